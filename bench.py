@@ -8,9 +8,21 @@ torus-knot tube, strands in front of strands, ~1.9x the interior visits per
 covered ray of the displaced-sphere blob (`--scene dragon`), which stays as a
 secondary line.  SURVEY.md §8d suggests the knot as the dragon stand-in.
 
-    python bench.py [--gpus N --steps K --warmup W]
+    python bench.py [--gpus N --steps K --warmup W] [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N \
         --master-addr 127.0.0.1 --master-port P bench.py --gpus N ...
+
+A plain run does what the headline figure needs and no more: it builds the
+scene, warms up, times the K frames, writes the last timed frame when
+--dump-outputs is given, and prints the result line (`value`, `ms_per_step`,
+`device_err`).  Everything else described below -- the roofline, the frame
+check against the oracle, the per-frame loop beside multi-frame launches, the
+timed shadow walk's counts, the per-rank gather times, the KD build timings
+on one thread and on the GPU, and the CPU baseline -- runs with --full only,
+where it works as before.  (The counting frames and the solo frames stay in a
+plain run, ~0.15 s together: they are the camera's first frames and the
+larger part of the warm-up, and the 20-frame headline ran 2-3 % low without
+them.  What they measure is reported with --full.)
 
 A step is one frame: bg fill -> primary rays -> KD traversal -> Moller-
 Trumbore -> Phong into the u32 frame (one fused kernel), plus, for N > 1,
@@ -29,7 +41,7 @@ The other BASELINE configs are selected with flags:
 and README.md:19's high-coverage view with --view fill.
 
 After the timed frames every line carries `device_err` (the camera's device
-error word; the run exits non-zero when it is set) and, at N = 1, a
+error word; the run exits non-zero when it is set) and, with --full at N = 1, a
 `frame_check`: the last timed frame against the oracle's committed full-frame
 hash (tests/golden/frame_hashes.json), or against an oracle render on this
 host when no hash matches.  With multi-frame launches as the headline (the
@@ -157,21 +169,54 @@ def parse():
                     help="CPU baseline threads (0: OMP_NUM_THREADS, else the CPUs this process may use)")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--traffic-json", default=os.path.join(ROOT, "profiles", "pmc_traffic.json"))
+    ap.add_argument("--full", action="store_true",
+                    help="also run and report everything beside the headline: the roofline (counts, the solo frames' "
+                         "kernel time), the frame check against the oracle, the per-frame loop (--second-frames), "
+                         "per-rank gather times, KD build timings (one thread, GPU) and the CPU baseline")
+    ap.add_argument("--dump-outputs", default="", metavar="DIR",
+                    help="after the timed frames write the last timed frame (rank 0's assembled frame at N > 1) "
+                         "as DIR/frame_argb.npy: float32 [height, width, 4], the A, R, G, B bytes of every u32 "
+                         "pixel (a fixed seeded sample of the pixels, with DIR/frame_pixels.npy naming them, when "
+                         "the frame exceeds 64 MB)")
     return ap.parse_args()
 
 
-def build_scene(name):
+DUMP_MAX_BYTES = 64 << 20
+DUMP_SEED = 20221015
+
+
+def dump_outputs(path, argb, w, h):
+    """Writes the u32 frame `argb` (w * h words, as the timed path left it) as
+    float32 A, R, G, B bytes under `path`; every value is an integer 0..255,
+    exact in float32.  A frame over DUMP_MAX_BYTES is sampled: the same
+    seeded, sorted pixel indices every run (frame_pixels.npy, float64)."""
+    os.makedirs(path, exist_ok=True)
+    words = np.ascontiguousarray(argb).reshape(-1).view(np.uint32)[: w * h]
+    chan = np.stack([(words >> s) & 0xFF for s in (24, 16, 8, 0)], -1).astype(np.float32)
+    keep = (DUMP_MAX_BYTES - (1 << 16)) // (chan.shape[1] * 4 + 8)  # sampled: 16 B of channels + 8 B of index each
+    if chan.nbytes <= DUMP_MAX_BYTES:
+        np.save(os.path.join(path, "frame_argb.npy"), chan.reshape(h, w, 4))
+        return
+    pix = np.sort(np.random.default_rng(DUMP_SEED).choice(w * h, size=keep, replace=False))
+    np.save(os.path.join(path, "frame_argb.npy"), chan[pix])
+    np.save(os.path.join(path, "frame_pixels.npy"), pix.astype(np.float64))
+
+
+def build_scene(name, full=True):
     """(points9, leafs, nodes, timings): read_ply's face assembly and the KD
-    build (a11) on this host, the build timed with all threads and one."""
+    build (a11) on this host, the build timed with all threads and, with
+    `full`, with one."""
     from cpp_cuda_raytracer_dev_amd import raytracer as R, scenes
     v, arity, idx = scenes.mesh_arrays(name)
     pts, n, leafs = R.assemble_mesh(v, scenes.faces_of(arity, idx))
     t0 = time.perf_counter()
     nodes = R.kd_build(leafs)
     t1 = time.perf_counter()
-    R.kd_build(leafs, nthreads=1)
-    t2 = time.perf_counter()
-    return pts, leafs, nodes, {"kd_build_s": round(t1 - t0, 4), "kd_build_s_1thread": round(t2 - t1, 4)}
+    times = {"kd_build_s": round(t1 - t0, 4)}
+    if full:
+        R.kd_build(leafs, nthreads=1)
+        times["kd_build_s_1thread"] = round(time.perf_counter() - t1, 4)
+    return pts, leafs, nodes, times
 
 
 def cpu_quota():
@@ -336,6 +381,8 @@ def cpu_only(a):
     fps, frames, dt = _oracle_fps(s, a.mode, (0, h), h, a.cpu_seconds, threads, a.shadow)
     fps1, frames1, dt1 = _oracle_fps(s, a.mode, (0, h), h, a.cpu_seconds, 1, a.shadow)
     s.close()
+    if a.dump_outputs:
+        dump_outputs(a.dump_outputs, argb, w, h)
     ent = reference_frame(a.scene, w, h, a.mode, a.shadow, a.view)
     got = hashlib.sha256(argb.tobytes()).hexdigest()
     rpf = w * h + (int((hit >= 0).sum()) if a.shadow else 0)
@@ -573,18 +620,19 @@ def main():
     w, h = a.width, a.height
 
     from cpp_cuda_raytracer_dev_amd import scenes
-    pts, leafs, nodes, build_times = build_scene(a.scene)
+    pts, leafs, nodes, build_times = build_scene(a.scene, a.full)
     # the same tree built on this GPU (rt_kd_build_gpu):
     # first call (allocations included) and a warm one, byte-checked
     gb = []
-    for _ in range(2):
+    for _ in range(2 if a.full else 0):
         t0 = time.perf_counter()
         gnodes = R.kd_build_gpu(leafs, device=local)
         gb.append(time.perf_counter() - t0)
-    build_times["kd_build_gpu_s"] = round(gb[1], 4)
-    build_times["kd_build_gpu_s_first"] = round(gb[0], 4)
-    build_times["kd_build_gpu_equals_host"] = gnodes.tobytes() == nodes.tobytes()
-    del gnodes
+    if gb:
+        build_times["kd_build_gpu_s"] = round(gb[1], 4)
+        build_times["kd_build_gpu_s_first"] = round(gb[0], 4)
+        build_times["kd_build_gpu_equals_host"] = gnodes.tobytes() == nodes.tobytes()
+        del gnodes
     trixel = R.Trixel(len(pts), pts, device=local)
     trixel.set_kd_nodes(nodes)
     if a.treelet > 0:
@@ -611,6 +659,13 @@ def main():
     scratch = torch.zeros(npk, dtype=torch.int32, device=dev)
     sflag = R.RT_FLAG_SHADOW if a.shadow else 0
     masks = key_masks(a.animate) if a.animate else []
+    # (The counting frames below stay in a plain run, a few ms: they are the
+    # camera's first frames, and the timed loop starts from the tile cost
+    # state they leave.  Without them its first 50 frames took 0.31 ms each
+    # instead of 0.08, the settle phase sized from those came out at 177
+    # frames instead of 490, and the 20-frame knot headline measured 11.9-
+    # 12.2k FPS against 12.5-12.6k, 5 runs each.  A plain run uses their
+    # counts for mray_per_s and coverage only; the roofline is --full's.)
     if masks:
         # every timed frame has its own pose: count each of them (untimed),
         # replaying the same ticks on a separate motion state
@@ -665,7 +720,8 @@ def main():
                     stream=sptr)  # re-prepares layout
     torch.cuda.synchronize(dev)
     my_pix = int(np.count_nonzero(np.repeat(np.arange((h + 7) // 8) % world == rank, 8)[:h])) * w
-    bytes_per_launch = B_INT * int(cnt[0]) + B_LEAF * int(cnt[1]) + B_HIT * int(cnt[2]) + B_PIX * my_pix
+    bytes_per_launch = (B_INT * int(cnt[0]) + B_LEAF * int(cnt[1]) + B_HIT * int(cnt[2]) + B_PIX * my_pix
+                        if cnt is not None else None)
 
     loop_kind = a.loop
     # --inflight -1: multi-frame launches (RT_LOOP_MULTIFRAME: one grid holds
@@ -838,6 +894,12 @@ def main():
         """(median batch mean ms, frames per batch) of solo frames, or None."""
         if isinstance(loop, PyLoop) or inflight <= 1 or a.solo_frames <= 0:
             return None
+        # (a plain run keeps this pass, ~0.1 s: its frames are the larger part
+        # of the headline's warm-up, warmup_breakdown.solo_pass, and the
+        # 20-frame headline without it and without the counting frames ran
+        # 2-3 % low; with both kept it equals --full's, 12.62k against
+        # 12.61k FPS over 5 runs each.  The pass alone was not left out.
+        # Only --full reports the kernel time it measures, in the roofline.)
         # the roofline's kernel time: solo frames (one in flight) back to
         # back, untimed, one event pair around the batch (per-frame event
         # pairs add ~5 us of queue time to each bracketed launch); the timed
@@ -951,12 +1013,20 @@ def main():
     # the timed frames' launch shape (before the per-frame loop below renders with its own)
     rays_used, fast_used = cam.get_option(_lib.RT_OPT_RAYS_USED), cam.get_option(_lib.RT_OPT_FAST_USED)
     frame_check = None
-    if not multi and rank == 0:
-        last = outs[loop.last_set()] if not isinstance(loop, PyLoop) else out
-        frame_check = frame_check_n1(last.cpu().numpy().view(np.uint32), pts, nodes, cam_kw, a,
-                                     xform=xf if masks else None)
+    if rank == 0 and (a.dump_outputs or (a.full and not multi)):
+        # the last timed frame, as a caller of the timed path receives it
+        # (N > 1: the frame rank 0 assembled from every rank's bands)
+        if multi:
+            last = ng.frames[loop.last_set()] if ng is not None else fg.frame
+        else:
+            last = outs[loop.last_set()] if not isinstance(loop, PyLoop) else out
+        last = last.cpu().numpy().view(np.uint32)
+        if a.dump_outputs:
+            dump_outputs(a.dump_outputs, last, w, h)
+        if a.full and not multi:
+            frame_check = frame_check_n1(last, pts, nodes, cam_kw, a, xform=xf if masks else None)
     per_frame_loop = None
-    if persistent and a.second_frames > 0:
+    if a.full and persistent and a.second_frames > 0:
         # VERDICT r04 item 7 / ADVICE r04: the headline batches copies of one
         # static frame per launch; the per-frame loop a moving scene would run
         # (rt_run_frames with two frames in flight on the render lanes, no
@@ -988,7 +1058,7 @@ def main():
         if err2:
             dev_err = dev_err or err2
     ranks_info = None
-    if multi:
+    if multi and a.full:
         ok = gathered_frame_ok(loop)
         if rank == 0:
             frame_check = {"gathered_equals_single_gpu_frame": ok,
@@ -1018,7 +1088,7 @@ def main():
         ranks_info = [None] * world
         dist.all_gather_object(ranks_info, mine)
     full_walk = None
-    if a.shadow and not masks:
+    if a.full and a.shadow and not masks:
         # shadow walks stop at their first occluder; the counting frame above
         # walked them in full (the oracle's counters).  Count the timed walk
         # (same push order) for the algorithmic bytes, untimed.
@@ -1037,16 +1107,19 @@ def main():
         t = torch.tensor([elapsed, kern_ms], dtype=torch.float64, device=dev)
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         elapsed, kern_ms_max = float(t[0]), float(t[1])
-        tb = torch.tensor([bytes_per_launch], dtype=torch.float64, device=dev)
-        dist.all_reduce(tb, op=dist.ReduceOp.MAX)
-        th = torch.tensor([int(cnt[3])], dtype=torch.float64, device=dev)
-        dist.all_reduce(th, op=dist.ReduceOp.SUM)
-        hits_all = int(th[0])
+        hits_all = None
+        if cnt is not None:
+            tb = torch.tensor([bytes_per_launch], dtype=torch.float64, device=dev)
+            dist.all_reduce(tb, op=dist.ReduceOp.MAX)
+            th = torch.tensor([int(cnt[3])], dtype=torch.float64, device=dev)
+            dist.all_reduce(th, op=dist.ReduceOp.SUM)
+            hits_all = int(th[0])
     else:
         kern_ms_max = kern_ms
-        hits_all = int(cnt[3])
+        hits_all = int(cnt[3]) if cnt is not None else None
     # rays per frame: every pixel's primary ray, plus a shadow ray per hit
-    rays_per_frame = w * h + (hits_all if a.shadow else 0)
+    # (the hit count comes from the counting frames: unknown without --full)
+    rays_per_frame = (w * h + (hits_all if a.shadow else 0)) if (hits_all is not None or not a.shadow) else None
 
     solo_before = (20 + len(batch_ms) * solo[1]) if (solo is not None and a.solo_when == "before") else 0
     if persistent:
@@ -1061,15 +1134,16 @@ def main():
     rc = 0
     if rank == 0:
         fps = a.steps / elapsed
-        achieved = bytes_per_launch / (kern_ms * 1e-3) / 1e9
+        # (the roofline's figures: --full; a plain run's line has "roofline": null)
+        achieved = bytes_per_launch / (kern_ms * 1e-3) / 1e9 if a.full else None
         tests = w * h * len(pts)  # flat list: every ray against every triangle
-        tflops = FLOPS_PER_TEST * tests / (kern_ms * 1e-3) / 1e12
+        tflops = FLOPS_PER_TEST * tests / (kern_ms * 1e-3) / 1e12 if a.full else None
         # counter-based figures of this configuration from the committed PMC
         # passes (tools/pmc_plan.py: one frame in flight, or with --own the
         # multi-frame launches of this loop, key suffix _mf; the same kernel),
         # stamped with the build id of the library they measured
         traffic, valu_util, pmc_key, pmc_build, vmem_util, vmem = None, None, None, None, None, None
-        if os.path.exists(a.traffic_json):
+        if a.full and os.path.exists(a.traffic_json):
             try:
                 tj = json.load(open(a.traffic_json))
                 key = (f"{a.scene}_{w}x{h}_m{a.mode}_n{world}" + ("_shadow" if a.shadow else "")
@@ -1129,7 +1203,7 @@ def main():
                                 + ("" if a.view == "default" else f" {a.view} view")),
             "value": round(fps, 2),
             "unit": "frames/s",
-            "mray_per_s": round(fps * rays_per_frame / 1e6, 2),
+            "mray_per_s": round(fps * rays_per_frame / 1e6, 2) if rays_per_frame is not None else None,
             "n_gpus": world,
             "steps": a.steps,
             "warmup": a.warmup,
@@ -1156,11 +1230,11 @@ def main():
                           if a.scene in scenes.STANDINS else f"{a.scene}.ply (the reference's mesh), {len(pts)} triangles"),
                 "resolution": [w, h],
                 "view": {"name": a.view, **cam_kw},
-                "coverage": round(hits_all / (w * h), 5),
+                "coverage": round(hits_all / (w * h), 5) if hits_all is not None else None,
                 "parallelism": f"screen bands x{world}" + ((" + RCCL send/recv to rank 0, pipelined" if collective == "rccl"
                                                          else f" + torch {collective} to rank 0") if multi else ""),
             },
-            "roofline": ({
+            "roofline": None if not a.full else ({
                 "bound": "valu",
                 "achieved": round(tflops, 2),
                 "peak": VALU_PEAK_TFLOPS,
@@ -1265,7 +1339,10 @@ def main():
                 frame_check = per_frame_loop["frame_check"]
         if a.deliver and world == 1:
             res["delivery"] = delivery(cam, R, torch, dev, w, h, xf, a.mode, sflag, a.steps, a.warmup)
-        if not a.no_cpu_baseline and world == 1:
+        res["full"] = a.full
+        if a.dump_outputs:
+            res["dump_outputs"] = a.dump_outputs
+        if a.full and not a.no_cpu_baseline and world == 1:
             res["cpu_baseline"] = cpu_baseline(pts, nodes, w, h, a.cpu_seconds, cpu_threads(a.cpu_threads), a.mode,
                                               a.shadow, rays_per_frame, cam_kw, build_times)
         else:

@@ -10,15 +10,17 @@ The reference's PLY files (data, not source) are stored as raw arrays:
 verts [nv,3] float32 parsed with C strtof (the rounding of read_ply's
 loader), arity [nf] int32 and idx (concatenated face indices).  Only
 vertices' first three fields are kept (the loader discards the rest,
-TD/read_ply.cpp:111-126).  Run in the container that has /root/reference.
+TD/read_ply.cpp:111-126).  The files themselves are kept under
+tests/golden/ply/ as they ship (rabbit_70k.ply xz-compressed).
 """
 import ctypes
+import lzma
 import os
 import sys
 
 import numpy as np
 
-REF = "/root/reference/TEST_Dungeonrun"
+REF = os.path.join(os.path.dirname(os.path.abspath(__file__)), "ply")
 OUT = os.path.join(os.path.dirname(os.path.abspath(__file__)), "meshes")
 MESHES = {"rabbit_70k": 5, "tester": 6, "dump": 5, "dump_test": 3}  # floats per vertex line
 
@@ -28,7 +30,8 @@ libc.strtof.argtypes = [ctypes.c_char_p, ctypes.c_void_p]
 
 
 def parse(path, per_vertex):
-    lines = open(path, "rb").read().split(b"\n")
+    raw = open(path, "rb").read() if os.path.exists(path) else lzma.open(path + ".xz").read()
+    lines = raw.split(b"\n")
     i = 0
     if lines[0].strip() == b"ply":
         i = 1

@@ -12,7 +12,7 @@ from cpp_cuda_raytracer_dev_amd import _lib, raytracer as R, scenes
 from oracle import _oracle as O, np_oracle as N
 from tests import helpers as H
 
-REF = "/root/reference/TEST_Dungeonrun"
+PLY_DIR = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "ply")
 HEADER = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "include", "rt_mi355x.h")
 
 
@@ -79,10 +79,22 @@ def test_mesh_assembly_matches_oracle(name):
     assert (leafs["tri"] == np.arange(n)).all()
 
 
-@pytest.mark.skipif(not os.path.isdir(REF), reason="reference meshes only in the build container")
+def _ply_file(name, tmp_path):
+    """Path of the reference's own <name>.ply (tests/golden/ply/: the file as
+    it ships, rabbit_70k.ply xz-compressed and unpacked into tmp_path)."""
+    path = os.path.join(PLY_DIR, name + ".ply")
+    if os.path.exists(path):
+        return path
+    import lzma
+    out = tmp_path / (name + ".ply")
+    with lzma.open(path + ".xz") as fp:
+        out.write_bytes(fp.read())
+    return str(out)
+
+
 @pytest.mark.parametrize("name,mode", list(scenes.FIXTURE_MODES.items()))
-def test_ply_loader_matches_oracle_and_fixture(name, mode):
-    path = os.path.join(REF, name + ".ply")
+def test_ply_loader_matches_oracle_and_fixture(name, mode, tmp_path):
+    path = _ply_file(name, tmp_path)
     pts, n, leafs = R.read_ply(path, mode)
     opts, oleafs = O.read_ply(path, mode)
     v, a, ix = scenes.fixture_mesh(name)

@@ -40,7 +40,7 @@ def main():
     if own:
         argv = argv[1:]
     key, ksub, args = argv[0], argv[1], argv[2:]
-    bench = ("python3 bench.py --steps 30 --warmup 5 --no-cpu-baseline "
+    bench = ("python3 bench.py --full --steps 30 --warmup 5 --no-cpu-baseline "
              + ("--solo-frames 0 " if own else "--inflight 1 ") + " ".join(shlex.quote(a) for a in args))
     print(f"# PMC passes of [{key}] ({ksub}): bench.py {' '.join(args)}")
     for name, ctrs in PASSES:

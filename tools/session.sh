@@ -8,10 +8,10 @@
 # bench JSON line is summarised.
 #   tools/session.sh <tag> <plan-file>
 # Plan shorthands:
-#   bench <args>            python bench.py <args>
+#   bench <args>            python bench.py --full <args> (every figure beside the headline too)
 #   smoke                   __graft_entry__.smoke()
 #   pytest <args>           the GPU test suite (-m gpu -x, 120 s per test)
-#   variant <lib> <args>    bench.py against tools/variants/lib_<lib>.so
+#   variant <lib> <args>    bench.py --full against tools/variants/lib_<lib>.so
 #   pmc <dir> <ctrs> -- <cmd...>   one rocprofv3 --pmc pass (counters only)
 #   stats <dir> -- <cmd...>        rocprofv3 --kernel-trace --stats
 #   trace <dir> -- <cmd...>        + --memory-copy-trace; traces kept gzipped (dir must start trace_)
@@ -51,10 +51,10 @@ while read -r name to rest; do
     unsetenv) unset "$to"; echo "== unsetenv $to"; continue ;;
     esac
     case $1 in
-    bench) shift; cmd=(python -u bench.py "$@") ;;
+    bench) shift; cmd=(python -u bench.py --full "$@") ;;
     smoke) cmd=(python -u -c "import __graft_entry__ as g; g.smoke()") ;;
     pytest) shift; cmd=(python -u -m pytest tests -m gpu -x -q -p no:cacheprovider --timeout 120 --timeout-method thread "$@") ;;
-    variant) shift; lib=$1; shift; cmd=(python -u tools/bench_variant.py "tools/variants/lib_$lib.so" "$@") ;;
+    variant) shift; lib=$1; shift; cmd=(python -u tools/bench_variant.py "tools/variants/lib_$lib.so" --full "$@") ;;
     pmc) shift; d=$1; shift; ctrs=(); while [ "$1" != "--" ]; do ctrs+=("$1"); shift; done; shift
          cmd=(rocprofv3 --pmc "${ctrs[@]}" --output-format csv -d "$OUT/$d" -o run -- "$@") ;;
     pmcsum) shift; k=$1; ks=$2; shift 2; ds=(); one=()
