@@ -23,6 +23,8 @@ RT_FLAG_WRITE_HIT = 1
 RT_FLAG_COUNT = 2
 RT_FLAG_SHADOW = 4
 RT_FLAG_FRAME_OUT = 8
+RT_FLAG_WRITE_AOV = 16
+RT_AOV_PLANES = 10
 RT_OPT_KERNEL = 1
 RT_OPT_TILE_ORDER = 2
 RT_OPT_RAYS = 3
@@ -133,6 +135,8 @@ SIGNATURES = {
     "rt_run_frames": (C.c_int, [_P, _P, C.POINTER(RtFrameLoop), C.c_int32, C.POINTER(C.c_int64),
                                 C.POINTER(C.c_double), C.POINTER(C.c_int32), C.POINTER(C.c_double)]),
     "rt_read_frame": (C.c_int, [_P, _P, _P]),
+    "rt_camera_set_aov": (C.c_int, [_P, _P, C.c_int64]),
+    "rt_read_aov": (C.c_int, [_P, _P]),
     "rt_camera_counters": (C.c_int, [_P, _P, C.c_int]),
     "rt_pinned_alloc": (C.c_int, [C.c_size_t, C.POINTER(_P)]),
     "rt_pinned_free": (None, [_P]),

@@ -70,6 +70,15 @@ struct rt_camera {
     rt_camera_basis_t basis{};
     uint32_t* d_argb = nullptr;
     int64_t* d_hit = nullptr;
+    // RT_FLAG_WRITE_AOV: the caller's planes (rt_camera_set_aov) or the
+    // camera's own, allocated by the first render that needs them; and the
+    // hit target of such a render whose caller passed none (the planes ride
+    // on the write-hit kernel instances)
+    float* aov_bound = nullptr;
+    int64_t aov_bound_stride = 0;
+    float* d_aov = nullptr;
+    bool aov_filled = false;         // a flagged render wrote d_aov (rt_read_aov)
+    int64_t* d_aov_hit = nullptr;
     unsigned long long* d_counters = nullptr;
     int32_t* d_err = nullptr;
     rt_scene* obj = nullptr;
@@ -1826,6 +1835,31 @@ struct PersistArgs {
     uint32_t* const* argb;
 };
 
+// The planes of a RT_FLAG_WRITE_AOV render split over nranks: the bound
+// buffer, which must hold the pixels such a render addresses (the packed band
+// buffer under a tile of several ranks, else the frame), or the camera's own,
+// whose stride holds the frame and any packed tile (every band, 8 rows each).
+static int aov_target(rt_camera* c, int32_t nranks, bool frame_out, float** aov, int64_t* stride) {
+    const int64_t npix = (int64_t)c->w * c->h;
+    if (c->aov_bound) {
+        const int64_t need = nranks > 1 && !frame_out ? rt_tile_packed_pixels(c->w, c->h, nranks) : npix;
+        if (c->aov_bound_stride < need)
+            return fail(RT_ERR_INVALID, "rt_render: plane stride %lld is below the %lld pixels this render writes",
+                        (long long)c->aov_bound_stride, (long long)need);
+        *aov = c->aov_bound;
+        *stride = c->aov_bound_stride;
+        return RT_OK;
+    }
+    *stride = rt_tile_packed_pixels(c->w, c->h, 1);
+    if (!c->d_aov) {
+        int rc = dev_alloc(&c->d_aov, (size_t)(RT_AOV_PLANES * *stride), "hipMalloc(aov)");
+        if (rc) return rc;
+    }
+    c->aov_filled = true;
+    *aov = c->d_aov;
+    return RT_OK;
+}
+
 static int render_common(rt_camera* c, const float* xform, uint32_t mode, uint32_t flags, const rt_tile* tile,
                          uint32_t* argb, int64_t* hit, void* stream, uint32_t* display = nullptr,
                          const PersistArgs* pf = nullptr, int32_t* rendered = nullptr) {
@@ -1840,7 +1874,7 @@ static int render_common(rt_camera* c, const float* xform, uint32_t mode, uint32
     if (mode == RT_MODE_KD && !c->obj->d_nodes)
         return fail(RT_ERR_STATE, "rt_render: KD mode needs rt_scene_set_kd (Trixel::create_kd) first");
     if (c->obj->ntri == 0) return fail(RT_ERR_STATE, "rt_render: empty scene");
-    if (flags & ~(RT_FLAG_WRITE_HIT | RT_FLAG_COUNT | RT_FLAG_SHADOW | RT_FLAG_FRAME_OUT))
+    if (flags & ~(RT_FLAG_WRITE_HIT | RT_FLAG_COUNT | RT_FLAG_SHADOW | RT_FLAG_FRAME_OUT | RT_FLAG_WRITE_AOV))
         return fail(RT_ERR_INVALID, "rt_render: unknown flags 0x%x", flags);
     if (flags & RT_FLAG_SHADOW) {
         if (mode != RT_MODE_KD) return fail(RT_ERR_INVALID, "rt_render: RT_FLAG_SHADOW needs RT_MODE_KD");
@@ -1851,6 +1885,17 @@ static int render_common(rt_camera* c, const float* xform, uint32_t mode, uint32
     static const float ident[12] = {1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1, 0};
     const float* xf = xform ? xform : ident;
     const int32_t nr = tile ? tile->nranks : 1, rk = tile ? tile->rank : 0;
+    float* aov = nullptr;
+    int64_t aov_stride = 0;
+    if (flags & RT_FLAG_WRITE_AOV) {
+        if ((rc = aov_target(c, nr, (flags & RT_FLAG_FRAME_OUT) != 0, &aov, &aov_stride))) return rc;
+        // the planes ride on the write-hit instances: those need a hit target
+        if (!hit) {
+            if (!c->d_aov_hit && (rc = dev_alloc(&c->d_aov_hit, (size_t)c->w * c->h, "hipMalloc(aov hit)"))) return rc;
+            hit = c->d_aov_hit;
+        }
+        flags |= RT_FLAG_WRITE_HIT;
+    }
     auto& pc = c->pcache;
     TraceParams p;
     if (pc.valid && !(c->debug & 2) && pc.gen == c->geom_gen && pc.tree == c->obj->tree_version && pc.mode == mode &&
@@ -1871,6 +1916,8 @@ static int render_common(rt_camera* c, const float* xform, uint32_t mode, uint32
     }
     p.frame_out = (flags & RT_FLAG_FRAME_OUT) ? 1 : 0;
     p.display = display;
+    p.aov = aov;
+    p.aov_stride = aov_stride;
     p.flat_key = nullptr;
     p.flat_chunks = 0;
     if (mode == RT_MODE_FLAT && c->flat_variant >= 10 && !(flags & RT_FLAG_COUNT)) {
@@ -2209,6 +2256,27 @@ extern "C" int rt_read_frame(rt_camera* c, uint32_t* argb, int64_t* hit) {
     return RT_OK;
 }
 
+extern "C" int rt_camera_set_aov(rt_camera* c, float* d_aov, int64_t plane_stride) {
+    if (!c) return fail(RT_ERR_INVALID, "rt_camera_set_aov: null camera");
+    if (d_aov && plane_stride <= 0) return fail(RT_ERR_INVALID, "rt_camera_set_aov: plane stride %lld", (long long)plane_stride);
+    c->aov_bound = d_aov;
+    c->aov_bound_stride = d_aov ? plane_stride : 0;
+    return RT_OK;
+}
+
+extern "C" int rt_read_aov(rt_camera* c, float* aov) {
+    if (!c || !aov) return fail(RT_ERR_INVALID, "rt_read_aov: null argument");
+    if (!c->aov_filled)
+        return fail(RT_ERR_STATE, "rt_read_aov: no RT_FLAG_WRITE_AOV render has filled the camera's own planes");
+    DeviceGuard g(c->device);
+    int rc;
+    if ((rc = hip_check(hipDeviceSynchronize(), "rt_read_aov sync"))) return rc;
+    // the planes of w*h floats out of the buffer's wider stride
+    const size_t row = (size_t)c->w * c->h * sizeof(float);
+    const size_t pitch = (size_t)rt_tile_packed_pixels(c->w, c->h, 1) * sizeof(float);
+    return hip_check(hipMemcpy2D(aov, row, c->d_aov, pitch, row, RT_AOV_PLANES, hipMemcpyDeviceToHost), "D2H aov");
+}
+
 extern "C" int rt_pinned_alloc(size_t bytes, void** out) {
     if (!out) return fail(RT_ERR_INVALID, "rt_pinned_alloc: null out");
     *out = nullptr;
@@ -2276,6 +2344,8 @@ extern "C" void rt_camera_destroy(rt_camera* c) {
     DeviceGuard g(c->device);
     dev_free(c->d_argb);
     dev_free(c->d_hit);
+    dev_free(c->d_aov);
+    dev_free(c->d_aov_hit);
     dev_free(c->d_counters);
     dev_free(c->d_err);
     dev_free(c->d_cam_flags);
@@ -2569,6 +2639,8 @@ extern "C" int rt_run_frames(rt_camera* c, rt_comm* comm, const rt_frame_loop* a
     if (!c || !a || !seq || nframes < 0 || a->nbuf < 1 || a->nbuf > RT_LOOP_MAX_BUF ||
         (a->inflight < 0 && a->inflight != RT_LOOP_MULTIFRAME) || a->inflight > RT_LOOP_MAX_LANES)
         return fail(RT_ERR_INVALID, "rt_run_frames: bad argument");
+    if (a->flags & RT_FLAG_WRITE_AOV)
+        return fail(RT_ERR_INVALID, "rt_run_frames: RT_FLAG_WRITE_AOV is not available in frame loops");
     if (a->inflight == RT_LOOP_MULTIFRAME) {
         if (comm || a->nxforms > 0)
             return fail(RT_ERR_INVALID, "rt_run_frames: multi-frame launches render a static scene without a gather");

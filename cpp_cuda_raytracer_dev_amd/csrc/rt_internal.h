@@ -180,6 +180,13 @@ struct TraceParams {
     // triangle) minima of the chunks, all ones between frames; and the chunk count
     unsigned long long* flat_key;
     int32_t flat_chunks;
+    // RT_FLAG_WRITE_AOV: ten float planes of aov_stride pixels each (d, pnt,
+    // norm, rad of the nearest hit: Camera::pixel_memory, TD/Camera.h:50-59),
+    // written by the write-hit instances next to the hit index; null = off.
+    // Last in the struct, so every earlier member keeps its kernel-argument
+    // offset and the instances that never read it stay as they were.
+    float* aov;
+    int64_t aov_stride;
 };
 
 // Blocks of k_trace_kd3's grid (fine tiles, split extras, far fill).

@@ -119,6 +119,35 @@ __device__ __forceinline__ void put_pixel(const TraceParams& P, int64_t out, uin
     base[out] = argb;
 }
 
+// RT_FLAG_WRITE_AOV (P.aov non-null, a wave-uniform test in the write-hit
+// instances only): the pixel's ten planes d, pnt, norm, rad -- what
+// intersect_voxel_cuda / intersect_trixel_cuda leave in Camera::pixel_memory
+// on an accepted hit (TD/Trixel.cu:127-140, :196), written once for the
+// nearest one.  One dword per lane and plane: a unit's row of 8 pixels is a
+// 32-byte run per plane.  Plain stores, like the frame's: either policy keeps
+// the line in L2 and the bytes leave it once, and the planes have no reader
+// on the device to bypass a cache for.
+__device__ __forceinline__ void put_aov(const TraceParams& P, int64_t out, float d, const float pnt[3],
+                                        const float nrm[3], const float rad[3]) {
+    float* a = P.aov + out;
+    const int64_t s = P.aov_stride;
+    a[0] = d;
+    a[s] = pnt[0]; a[2 * s] = pnt[1]; a[3 * s] = pnt[2];
+    a[4 * s] = nrm[0]; a[5 * s] = nrm[1]; a[6 * s] = nrm[2];
+    a[7 * s] = rad[0]; a[8 * s] = rad[1]; a[9 * s] = rad[2];
+}
+// A miss: the draw distance init_cam_mem_cuda stores (TD/Camera.cu:109) and
+// zeros (the reference leaves whatever an earlier frame's hit wrote there).
+__device__ __forceinline__ void put_aov_miss(const TraceParams& P, int64_t out) {
+    const float zero[3] = {0.0f, 0.0f, 0.0f};
+    put_aov(P, out, kDrawDistance, zero, zero, zero);
+}
+// A background writer's pixel in a write-hit instance: no hit, and its planes.
+__device__ __forceinline__ void put_miss(const TraceParams& P, int64_t out) {
+    P.hit[out] = (int64_t)-1;
+    if (P.aov) put_aov_miss(P, out);
+}
+
 // Block -> tile.  Order 0: blocks b and b+8 share an XCD, so give each XCD a
 // contiguous run of tiles (bijective for any grid size); order 1: natural
 // (neighbouring tiles on different XCDs); order 2: the host's centre-out
@@ -290,6 +319,33 @@ struct Ray {
     float ox, oy, oz;          // od / r
     bool sx, sy, sz;           // r > 0
 };
+
+// The nearest-hit writes of TD/Trixel.cu:128-140, done once for the final hit
+// (w = d, triangle best): the hit point, the rotated normal, the radiance.
+__device__ __forceinline__ void kd_hit_values(const TraceParams& P, const Ray& R, float d, uint32_t best,
+                                              float pnt[3], float nrm[3], float rad[3]) {
+    const float* X = P.xf;
+    const float4 N = P.shade[2 * (size_t)best];
+    const float4 M = P.shade[2 * (size_t)best + 1];
+    pnt[0] = d * R.rx + R.odx; pnt[1] = d * R.ry + R.ody; pnt[2] = d * R.rz + R.odz;
+    // norm.device_rotate(rot_m, i, -1), TD/vector.cuh:23-33
+    const float ax = -1 * N.x, ay = -1 * N.y, az = -1 * N.z;
+    nrm[0] = (ax * X[0] + ay * X[1] + az * X[2]) * -1;
+    nrm[1] = (ax * X[4] + ay * X[5] + az * X[6]) * -1;
+    nrm[2] = (ax * X[8] + ay * X[9] + az * X[10]) * -1;
+    rad[0] = M.x; rad[1] = M.y; rad[2] = M.z;
+}
+
+// A KD pixel's hit index in a write-hit instance, and its planes
+// (RT_FLAG_WRITE_AOV): the primary hit's, whatever a shadow ray found.
+__device__ __forceinline__ void put_hit_kd(const TraceParams& P, int64_t out, const Ray& R, float d, uint32_t best) {
+    P.hit[out] = best == kMiss ? (int64_t)-1 : (int64_t)best;
+    if (!P.aov) return;
+    if (best == kMiss) return put_aov_miss(P, out);
+    float pnt[3], nrm[3], rad[3];
+    kd_hit_values(P, R, d, best, pnt, nrm, rad);
+    put_aov(P, out, d, pnt, nrm, rad);
+}
 
 typedef float f2v __attribute__((ext_vector_type(2)));
 
@@ -609,11 +665,11 @@ __global__ __launch_bounds__(kTileWKd * kTileH) void k_trace_kd2(TraceParams P) 
 
     uint32_t argb = kBackground;
     if (best != kMiss) {
-        // nearest-hit writes of TD/Trixel.cu:128-140, done once for the final hit
+        // kd_hit_values, spelled out as before it existed: through the helper
+        // the counting instance without a hit buffer allocates 60 VGPRs for 58
         const float4 N = P.shade[2 * (size_t)best];
         const float4 M = P.shade[2 * (size_t)best + 1];
         const float pnt[3] = {d * R.rx + R.odx, d * R.ry + R.ody, d * R.rz + R.odz};
-        // norm.device_rotate(rot_m, i, -1), TD/vector.cuh:23-33
         const float ax = -1 * N.x, ay = -1 * N.y, az = -1 * N.z;
         const float nrm[3] = {(ax * X[0] + ay * X[1] + az * X[2]) * -1,
                               (ax * X[4] + ay * X[5] + az * X[6]) * -1,
@@ -622,7 +678,7 @@ __global__ __launch_bounds__(kTileWKd * kTileH) void k_trace_kd2(TraceParams P) 
         argb = phong(pnt, nrm, cam, rad);
     }
     put_pixel(P, px.out, argb, best != kMiss);
-    if (kWriteHit) P.hit[px.out] = best == kMiss ? (int64_t)-1 : (int64_t)best;
+    if (kWriteHit) put_hit_kd(P, px.out, R, d, best);
     if (kCount) {
         wave_count_add(&P.counters[0], n_int);
         wave_count_add(&P.counters[1], n_leaf);
@@ -2031,25 +2087,17 @@ struct Counts {
 template <bool kWriteHit, bool kCount>
 __device__ __forceinline__ void shade_out(const TraceParams& P, const Pixel& px, const Ray& R, const float cam[3],
                                           unsigned long long kbest, uint32_t best, bool shadowed, Counts& C) {
-    const float* X = P.xf;
+    const float d = __uint_as_float((uint32_t)(kbest >> 32));  // of a hit
     uint32_t argb = kBackground;
     if (shadowed) {
         argb = 0x00000000u;  // point_rad stays 0: 0/0 -> (u8)NaN = 0 (H14)
     } else if (best != kMiss) {
-        const float d = __uint_as_float((uint32_t)(kbest >> 32));
-        const float4 N = P.shade[2 * (size_t)best];
-        const float4 M = P.shade[2 * (size_t)best + 1];
-        const float pnt[3] = {d * R.rx + R.odx, d * R.ry + R.ody, d * R.rz + R.odz};
-        // norm.device_rotate(rot_m, i, -1), TD/vector.cuh:23-33
-        const float ax = -1 * N.x, ay = -1 * N.y, az = -1 * N.z;
-        const float nrm[3] = {(ax * X[0] + ay * X[1] + az * X[2]) * -1,
-                              (ax * X[4] + ay * X[5] + az * X[6]) * -1,
-                              (ax * X[8] + ay * X[9] + az * X[10]) * -1};
-        const float rad[3] = {M.x, M.y, M.z};
+        float pnt[3], nrm[3], rad[3];
+        kd_hit_values(P, R, d, best, pnt, nrm, rad);
         argb = phong(pnt, nrm, cam, rad);
     }
     put_pixel(P, px.out, argb, best != kMiss);
-    if (kWriteHit) P.hit[px.out] = best == kMiss ? (int64_t)-1 : (int64_t)best;
+    if (kWriteHit) put_hit_kd(P, px.out, R, d, best);
     if (kCount && best != kMiss) C.n_hit++;
 }
 
@@ -2453,7 +2501,7 @@ __device__ __forceinline__ bool fill_far(const TraceParams& P, const Unit& G, in
     if (!P.far_all && __ballot(live && ray_has_tiny_component(P, px.x, px.y)) != 0ull) return false;
     if (live) {
         put_pixel(P, px.out, kBackground, false);
-        if (kWriteHit) P.hit[px.out] = (int64_t)-1;
+        if (kWriteHit) put_miss(P, px.out);
         if (kCount) C.n_int += 1u;  // the root visit, which fails
     }
     return true;
@@ -2465,7 +2513,7 @@ __device__ __forceinline__ void fill_background(const TraceParams& P, const Unit
     Pixel px;
     if (unit_pixel(P, G, 8, lane, px)) {
         put_pixel(P, px.out, kBackground, false);
-        if (kWriteHit) P.hit[px.out] = (int64_t)-1;
+        if (kWriteHit) put_miss(P, px.out);
         if (kCount) C.n_int += 1u;  // the root visit, which fails
     }
 }
@@ -2480,7 +2528,7 @@ __device__ __forceinline__ bool coarse_sure(const TraceParams& P, const Unit& G,
     if (__ballot(!sure) != 0ull) return false;
     if (live) {
         put_pixel(P, px.out, kBackground, false);
-        if (kWriteHit) P.hit[px.out] = (int64_t)-1;
+        if (kWriteHit) put_miss(P, px.out);
         if (kCount) C.n_int += 1u;  // the root visit, which fails
     }
     return true;
@@ -2501,7 +2549,7 @@ __device__ __forceinline__ unsigned long long coarse_root(const TraceParams& P, 
     const bool traced = ((b >> ((lane / kRays) * kRays)) & kSub) != 0;
     if (live && !traced) {
         put_pixel(P, px.out, kBackground, false);
-        if (kWriteHit) P.hit[px.out] = (int64_t)-1;
+        if (kWriteHit) put_miss(P, px.out);
         if (kCount) C.n_int += ni;  // the root visit; no root test passed in this sub-tile
     }
     return b;
@@ -2749,6 +2797,9 @@ __device__ __forceinline__ void flat_shade_out(const TraceParams& P, const Pixel
         const float nrm[3] = {N.x, N.y, N.z};
         const float rad[3] = {M.x, M.y, M.z};
         argb = phong(pnt, nrm, rmd, rad);
+        if (kWriteHit && P.aov) put_aov(P, px.out, d, pnt, nrm, rad);
+    } else if (kWriteHit && P.aov) {
+        put_aov_miss(P, px.out);
     }
     put_pixel(P, px.out, argb, best != kMiss);
     if (kWriteHit) P.hit[px.out] = best == kMiss ? (int64_t)-1 : (int64_t)best;

@@ -25,8 +25,8 @@ import sys
 import numpy as np
 
 from . import _lib
-from ._lib import (KD_NODE_DTYPE, LEAF_AABB_DTYPE, RT_FLAG_COUNT, RT_FLAG_FRAME_OUT, RT_FLAG_SHADOW, RT_FLAG_WRITE_HIT,
-                   RT_MODE_FLAT, RT_MODE_KD)
+from ._lib import (KD_NODE_DTYPE, LEAF_AABB_DTYPE, RT_AOV_PLANES, RT_FLAG_COUNT, RT_FLAG_FRAME_OUT, RT_FLAG_SHADOW,
+                   RT_FLAG_WRITE_AOV, RT_FLAG_WRITE_HIT, RT_MODE_FLAT, RT_MODE_KD)
 
 SET_COLOR_TAG = 1      # TD/Camera.h:13
 PHONG_COLOR_TAG = 2    # TD/Camera.h:14
@@ -350,8 +350,38 @@ class Camera:
         self._last_flags = flags
         return 0
 
-    def render_into(self, argb, hit=None, xform=None, mode=RT_MODE_KD, flags=0, tile=None, stream=None) -> int:
-        """Render into caller-owned device buffers (torch tensors or raw pointers)."""
+    def set_aov(self, aov=None, plane_stride=None) -> None:
+        """rt_camera_set_aov: bind a caller-owned device buffer (a float32
+        torch tensor or a raw pointer) of 10 * plane_stride floats for renders
+        with RT_FLAG_WRITE_AOV; ``None`` returns to the camera's own buffer.
+        plane_stride defaults to a tensor's element count // 10."""
+        if aov is None:
+            _lib.call("rt_camera_set_aov", self._h, None, 0)
+        else:
+            if plane_stride is None:
+                plane_stride = aov.numel() // RT_AOV_PLANES
+            a = aov if isinstance(aov, C.c_void_p) else _lib.ptr(aov)
+            _lib.call("rt_camera_set_aov", self._h, a, int(plane_stride))
+        self._aov = aov  # keeps a bound tensor alive
+
+    def aov(self) -> dict:
+        """rt_read_aov: the camera's own planes of the last RT_FLAG_WRITE_AOV
+        render as float32 arrays (row 0 = bottom): {"d": [h, w], "pnt": [3, h,
+        w], "norm": [3, h, w], "rad": [3, h, w]}.  A miss holds d = 400 and
+        zeros elsewhere."""
+        w, h = self.res
+        buf = np.empty((RT_AOV_PLANES, h, w), np.float32)
+        _lib.call("rt_read_aov", self._h, _lib.ptr(buf))
+        return {"d": buf[0], "pnt": buf[1:4], "norm": buf[4:7], "rad": buf[7:10]}
+
+    def render_into(self, argb, hit=None, xform=None, mode=RT_MODE_KD, flags=0, tile=None, stream=None,
+                    aov=None, plane_stride=None) -> int:
+        """Render into caller-owned device buffers (torch tensors or raw pointers).
+        aov: also bind that plane buffer (``set_aov``) and render with
+        RT_FLAG_WRITE_AOV; it stays bound."""
+        if aov is not None:
+            self.set_aov(aov, plane_stride)
+            flags |= RT_FLAG_WRITE_AOV
         xf = np.ascontiguousarray(xform if xform is not None else Quaternion().xform(), np.float32)
         t = None if tile is None else C.byref(_lib.RtTile(tile[0], tile[1]))
         s = C.c_void_p(stream) if isinstance(stream, int) else C.c_void_p(None)
@@ -514,4 +544,4 @@ class PinnedFrames:
 
 __all__ = ["read_ply", "assemble_mesh", "kd_build", "film_w", "camera_basis", "Quaternion", "Trixel", "Object",
            "Camera", "PinnedFrames", "packed_pixels", "unpack_bands", "SET_COLOR_TAG", "PHONG_COLOR_TAG", "RT_MODE_KD",
-           "RT_MODE_FLAT", "RT_FLAG_WRITE_HIT", "RT_FLAG_COUNT", "RT_FLAG_SHADOW", "RT_FLAG_FRAME_OUT", "BACKGROUND_ARGB", "DEFAULT_RAD"]
+           "RT_MODE_FLAT", "RT_FLAG_WRITE_HIT", "RT_FLAG_COUNT", "RT_FLAG_SHADOW", "RT_FLAG_FRAME_OUT", "RT_FLAG_WRITE_AOV", "BACKGROUND_ARGB", "DEFAULT_RAD"]

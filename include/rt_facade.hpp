@@ -183,6 +183,13 @@ public:
     struct pixel_memory {
         struct { u32* c = nullptr; } h_color;      // the frame, 0x00RRGGBB, row 0 = bottom
         struct { s64* index = nullptr; } h_rmi;    // hit triangle per pixel (-1 miss)
+        // host mirrors of the nearest hit's per-pixel results, with the names
+        // of the reference's device arrays (TD/Camera.h:50-59): null until
+        // write_pixel_memory(true), then one float per pixel each, filled by
+        // color_pixels (a miss: d = 400, zeros elsewhere; rt_mi355x.h)
+        struct { T_fp* d = nullptr; } d_dist;                     // hit distance w
+        struct { T_fp *x = nullptr, *y = nullptr, *z = nullptr; } pnt, norm;  // hit point, rotated normal
+        struct { T_fp *r = nullptr, *g = nullptr, *b = nullptr; } rad;        // the triangle's radiance
     } h_mem;
     int status = RT_OK;
 
@@ -222,13 +229,28 @@ public:
     // (and the hit buffer when the last render wrote one).
     int color_pixels(u8 color_tag_select = PHONG_COLOR_TAG) {
         (void)color_tag_select;  // both tags show the steady-state frame
-        return rt_read_frame(cam_, h_mem.h_color.c, write_hit_ ? h_mem.h_rmi.index : nullptr);
+        int rc = rt_read_frame(cam_, h_mem.h_color.c, write_hit_ ? h_mem.h_rmi.index : nullptr);
+        return rc || !write_aov_ ? rc : rt_read_aov(cam_, aov_.data());
     }
 
     int render_with(const Quaternion* q, u32 mode) {
-        return rt_render(cam_, q ? q->rot_m : nullptr, mode, write_hit_ ? RT_FLAG_WRITE_HIT : 0u, nullptr, nullptr);
+        const u32 flags = (write_hit_ ? RT_FLAG_WRITE_HIT : 0u) | (write_aov_ ? RT_FLAG_WRITE_AOV : 0u);
+        return rt_render(cam_, q ? q->rot_m : nullptr, mode, flags, nullptr, nullptr);
     }
     void keep_hit_buffer(bool on) { write_hit_ = on; }
+    // Renders also write the per-pixel hit results (RT_FLAG_WRITE_AOV) and
+    // color_pixels copies them to h_mem.d_dist / pnt / norm / rad.
+    void write_pixel_memory(bool on) {
+        write_aov_ = on;
+        if (!on || !aov_.empty()) return;
+        const size_t n = (size_t)f_prop.res.count;
+        aov_.assign(RT_AOV_PLANES * n, 0.0f);
+        T_fp* a = aov_.data();
+        h_mem.d_dist.d = a;
+        h_mem.pnt.x = a + n; h_mem.pnt.y = a + 2 * n; h_mem.pnt.z = a + 3 * n;
+        h_mem.norm.x = a + 4 * n; h_mem.norm.y = a + 5 * n; h_mem.norm.z = a + 6 * n;
+        h_mem.rad.r = a + 7 * n; h_mem.rad.g = a + 8 * n; h_mem.rad.b = a + 9 * n;
+    }
     rt_camera* handle() const { return cam_; }
     T_fp cam_speed = .005f;  // TD/WinMain.cpp:170
 
@@ -238,7 +260,8 @@ private:
     std::vector<u32> color_;
     std::vector<s64> rmi_;
     std::vector<Object*> objects_;
-    bool write_hit_ = false;
+    std::vector<T_fp> aov_;  // the ten planes h_mem's mirrors point into
+    bool write_hit_ = false, write_aov_ = false;
 };
 
 inline int Trixel::intersect_trixels(Camera* c, Quaternion* q, u32 m) { return c->render_with(q, m); }

@@ -58,6 +58,25 @@ typedef enum rt_status {
  * ranks' bands are not touched.  Rank 0 of a gather renders straight into
  * the frame it assembles (rt_comm_gather_frame with d_local == d_frame). */
 #define RT_FLAG_FRAME_OUT 8u
+/* Also write the nearest hit's per-pixel results, the reference's
+ * Camera::pixel_memory (TD/Camera.h:50-59; written by intersect_voxel_cuda /
+ * intersect_trixel_cuda on every accepted hit, TD/Trixel.cu:127-140, :196,
+ * read by color_cam_cuda): ten float planes in the order d (d_dist.d, the hit
+ * distance w), pnt.x pnt.y pnt.z (the hit point), norm.x norm.y norm.z (the
+ * rotated normal), rad.r rad.g rad.b (d_color.rad).  Planar like the
+ * reference's VEC3_CUDA arrays: plane k of pixel i is aov[k * plane_stride +
+ * i], i being the index the frame uses (the packed band slot under a tile,
+ * the frame position under RT_FLAG_FRAME_OUT or without a tile).  A hit
+ * pixel holds the reference's values bit for bit.  A miss pixel holds
+ * d = 400.0f (the draw distance init_cam_mem_cuda stores, TD/Camera.cu:109)
+ * and zeros in the other nine planes: this is this library's definition, the
+ * reference leaves there whatever an earlier frame's hit wrote.  Under
+ * RT_FLAG_SHADOW the planes are the primary hit's, shadowed or not.  The
+ * planes go to the buffer rt_camera_set_aov bound, else to the camera's own
+ * (rt_read_aov).  Every render entry point, mode, KD kernel, tile and
+ * transform takes it; rt_run_frames rejects it. */
+#define RT_FLAG_WRITE_AOV 16u
+#define RT_AOV_PLANES 10
 
 /* Per-triangle AABB = kd_leaf (TD/Trixel.h:31-37); `tri` = tri_list_index. */
 typedef struct rt_leaf_aabb {
@@ -355,6 +374,23 @@ int rt_run_frames(rt_camera* cam, rt_comm* comm, const rt_frame_loop* loop, int3
 /* The D2H copy of color_camera_device (TD/Camera.cu:84) and d_rmi.index.
  * Synchronises the device.  argb: w*h u32 0x00RRGGBB; hit may be NULL. */
 int rt_read_frame(rt_camera* c, uint32_t* argb, int64_t* hit);
+
+/* Where RT_FLAG_WRITE_AOV renders of this camera write their planes: a
+ * caller-owned device buffer of RT_AOV_PLANES * plane_stride floats, or
+ * (d_aov NULL, the initial state) the camera's own, allocated by the first
+ * such render with a stride that holds the full frame and any packed tile.
+ * A render whose pixels (the packed pixels of a tile of several ranks, else
+ * w*h) exceed plane_stride returns RT_ERR_INVALID before anything is
+ * launched.  Pixels a render does not write (other ranks' rows under
+ * RT_FLAG_FRAME_OUT) are not touched. */
+int rt_camera_set_aov(rt_camera* c, float* d_aov, int64_t plane_stride);
+
+/* rt_read_frame's sibling for the camera's own planes (the reference has no
+ * D2H of d_mem; its host mirror h_mem is what rt_facade.hpp fills from this):
+ * synchronises the device and copies RT_AOV_PLANES planes of w*h floats,
+ * plane k at aov + k*w*h.  RT_ERR_STATE when no RT_FLAG_WRITE_AOV render has
+ * written them. */
+int rt_read_aov(rt_camera* c, float* aov);
 
 /* Frame delivery: the reference copies every frame
  * to the host synchronously (cudaMemcpy in color_camera_device,

@@ -1,7 +1,7 @@
 // rt_headless.cpp -- the headless frame loop that replaces WinMain
 // (TD/WinMain.cpp:44-249), written against the reference-shaped C++ facade.
 //
-//   rt_headless <mesh.ply> <mode 0|1|2> [w h frames out.ppm flat keys]
+//   rt_headless <mesh.ply> <mode 0|1|2> [w h frames out.ppm flat keys] [--aov planes.f32]
 //
 // keys: held keys per frame, cycled, one input tick per frame (WinMain ticks
 // at TICK_RATE, :173): letters of R W S Q E T, '+' joins keys held together,
@@ -14,6 +14,7 @@
 #include <chrono>
 #include <cstdio>
 #include <cstdlib>
+#include <cstring>
 #include <vector>
 
 #include "rt_facade.hpp"
@@ -25,8 +26,19 @@ static double now_s() {
 }
 
 int main(int argc, char** argv) {
+    // --aov FILE (anywhere on the line): also keep the per-pixel hit results
+    // (Camera::write_pixel_memory) and write the last frame's ten planes
+    // (d, pnt.xyz, norm.xyz, rad.rgb; w*h floats each, row 0 = bottom) as raw float32
+    const char* aov_out = nullptr;
+    for (int k = 1; k + 1 < argc; k++)
+        if (!std::strcmp(argv[k], "--aov")) {
+            aov_out = argv[k + 1];
+            for (int j = k; j + 2 < argc; j++) argv[j] = argv[j + 2];
+            argc -= 2;
+            break;
+        }
     if (argc < 3) {
-        std::fprintf(stderr, "usage: %s mesh.ply mode [w h frames out.ppm flat]\n", argv[0]);
+        std::fprintf(stderr, "usage: %s mesh.ply mode [w h frames out.ppm flat keys] [--aov planes.f32]\n", argv[0]);
         return 2;
     }
     const char* mesh = argv[1];
@@ -54,6 +66,7 @@ int main(int argc, char** argv) {
     Camera* main_cam = new Camera(w, h, film_w(w, h), (T_fp).024, (T_fp).055, (T_fp)0.0, (T_fp)0.10, (T_fp)-1.0,
                                   (T_fp)0.00, (T_fp)0.100, (T_fp)0.00, (T_fp)0.0, (T_fp)1.0, (T_fp)0.0);
     if (main_cam->status) { std::fprintf(stderr, "Camera: %s\n", rt_last_error_string()); return 1; }
+    if (aov_out) main_cam->write_pixel_memory(true);
 
     T_fp* points = nullptr;
     kd_leaf_sort* leafs = nullptr;
@@ -116,6 +129,17 @@ int main(int argc, char** argv) {
                 std::fwrite(px, 1, 3, fp);
             }
         std::fclose(fp);
+    }
+    if (aov_out) {
+        FILE* fp = std::fopen(aov_out, "wb");
+        if (!fp) { std::perror(aov_out); return 1; }
+        const auto& m = main_cam->h_mem;
+        const T_fp* planes[RT_AOV_PLANES] = {m.d_dist.d, m.pnt.x, m.pnt.y, m.pnt.z, m.norm.x,
+                                             m.norm.y, m.norm.z, m.rad.r, m.rad.g, m.rad.b};
+        const size_t n = (size_t)w * (size_t)h;
+        bool ok = true;
+        for (const T_fp* p : planes) ok = ok && std::fwrite(p, sizeof(T_fp), n, fp) == n;
+        if (std::fclose(fp) || !ok) { std::perror(aov_out); return 1; }
     }
     delete obj1;
     delete obj2;
