@@ -1862,7 +1862,7 @@ static int aov_target(rt_camera* c, int32_t nranks, bool frame_out, float** aov,
 
 static int render_common(rt_camera* c, const float* xform, uint32_t mode, uint32_t flags, const rt_tile* tile,
                          uint32_t* argb, int64_t* hit, void* stream, uint32_t* display = nullptr,
-                         const PersistArgs* pf = nullptr, int32_t* rendered = nullptr) {
+                         const PersistArgs* pf = nullptr, int32_t* rendered = nullptr, const int64_t* over_base = nullptr) {
     if (rendered) *rendered = 1;
     if (!c) return fail(RT_ERR_INVALID, "rt_render: null camera");
     if (mode != RT_MODE_KD && mode != RT_MODE_FLAT) return fail(RT_ERR_INVALID, "rt_render: mode %u", mode);
@@ -1887,6 +1887,11 @@ static int render_common(rt_camera* c, const float* xform, uint32_t mode, uint32
     const int32_t nr = tile ? tile->nranks : 1, rk = tile ? tile->rank : 0;
     float* aov = nullptr;
     int64_t aov_stride = 0;
+    // rt_render_over reads the d it tests against: the camera's own planes
+    // must hold a frame (a bound buffer is the caller's to fill)
+    if (over_base && !c->aov_bound && !c->aov_filled)
+        return fail(RT_ERR_STATE, "rt_render_over: the camera's own planes hold no frame (render with "
+                                  "RT_FLAG_WRITE_AOV or rt_render_clear first)");
     if (flags & RT_FLAG_WRITE_AOV) {
         if ((rc = aov_target(c, nr, (flags & RT_FLAG_FRAME_OUT) != 0, &aov, &aov_stride))) return rc;
         // the planes ride on the write-hit instances: those need a hit target
@@ -1918,6 +1923,8 @@ static int render_common(rt_camera* c, const float* xform, uint32_t mode, uint32
     p.display = display;
     p.aov = aov;
     p.aov_stride = aov_stride;
+    p.over = over_base ? 1 : 0;
+    p.hit_base = over_base ? *over_base : 0;
     p.flat_key = nullptr;
     p.flat_chunks = 0;
     if (mode == RT_MODE_FLAT && c->flat_variant >= 10 && !(flags & RT_FLAG_COUNT)) {
@@ -2031,6 +2038,57 @@ extern "C" int rt_render_display(rt_camera* c, const float* xform, uint32_t mode
 extern "C" int rt_render_into(rt_camera* c, const float* xform, uint32_t mode, uint32_t flags, const rt_tile* tile,
                               uint32_t* d_argb, int64_t* d_hit, void* stream) {
     return render_common(c, xform, mode, flags, tile, d_argb, d_hit, stream);
+}
+
+extern "C" int rt_render_over(rt_camera* c, const float* xform, uint32_t mode, uint32_t flags, const rt_tile* tile,
+                              uint32_t* d_argb, int64_t* d_hit, int64_t hit_base, void* stream) {
+    if (!c) return fail(RT_ERR_INVALID, "rt_render_over: null camera");
+    if (flags & ~(RT_FLAG_WRITE_HIT | RT_FLAG_COUNT | RT_FLAG_SHADOW | RT_FLAG_FRAME_OUT | RT_FLAG_WRITE_AOV))
+        return fail(RT_ERR_INVALID, "rt_render_over: unknown flags 0x%x", flags);
+    if (hit_base < 0) return fail(RT_ERR_INVALID, "rt_render_over: hit_base %lld", (long long)hit_base);
+    // no targets: the camera's own frame and hit buffers; a frame alone:
+    // no hit index is kept (render_common's scratch takes the stores)
+    if (!d_argb) {
+        d_argb = c->d_argb;
+        if (!d_hit) d_hit = c->d_hit;
+    }
+    // RT_FLAG_WRITE_AOV brings the write-hit instances (and that scratch) with it
+    return render_common(c, xform, mode, (flags & ~RT_FLAG_WRITE_HIT) | RT_FLAG_WRITE_AOV, tile, d_argb, d_hit, stream,
+                         nullptr, nullptr, nullptr, &hit_base);
+}
+
+extern "C" int rt_render_clear(rt_camera* c, uint32_t flags, const rt_tile* tile, uint32_t* d_argb, int64_t* d_hit,
+                               void* stream) {
+    if (!c) return fail(RT_ERR_INVALID, "rt_render_clear: null camera");
+    if (flags & ~RT_FLAG_FRAME_OUT) return fail(RT_ERR_INVALID, "rt_render_clear: unknown flags 0x%x", flags);
+    int rc = check_tile(tile);
+    if (rc) return rc;
+    if (!d_argb) {
+        d_argb = c->d_argb;
+        if (!d_hit) d_hit = c->d_hit;
+    }
+    DeviceGuard g(c->device);
+    const int32_t nr = tile ? tile->nranks : 1, rk = tile ? tile->rank : 0;
+    const bool frame_out = (flags & RT_FLAG_FRAME_OUT) != 0;
+    float* aov = nullptr;
+    int64_t stride = 0;
+    if ((rc = aov_target(c, nr, frame_out, &aov, &stride))) return rc;  // marks the camera's own planes filled
+    return launch_clear(c->w, c->h, nr, rk, frame_out, d_argb, d_hit, aov, stride, stream);
+}
+
+extern "C" int rt_camera_targets(rt_camera* c, uint32_t** d_argb, int64_t** d_hit, float** d_aov, int64_t* plane_stride) {
+    if (!c) return fail(RT_ERR_INVALID, "rt_camera_targets: null camera");
+    const int64_t stride = rt_tile_packed_pixels(c->w, c->h, 1);
+    if (d_aov && !c->d_aov) {
+        DeviceGuard g(c->device);
+        int rc = dev_alloc(&c->d_aov, (size_t)(RT_AOV_PLANES * stride), "hipMalloc(aov)");
+        if (rc) return rc;
+    }
+    if (d_argb) *d_argb = c->d_argb;
+    if (d_hit) *d_hit = c->d_hit;
+    if (d_aov) *d_aov = c->d_aov;
+    if (plane_stride) *plane_stride = stride;
+    return RT_OK;
 }
 
 extern "C" int64_t rt_tile_packed_pixels(int32_t w, int32_t h, int32_t nranks) {

@@ -187,6 +187,12 @@ struct TraceParams {
     // offset and the instances that never read it stay as they were.
     float* aov;
     int64_t aov_stride;
+    // rt_render_over (after the planes for the same reason): a pixel is
+    // written only where it is a hit nearer than plane 0's d, with hit_base
+    // added to its triangle index; every other pixel gets no store.  Read by
+    // the write-hit instances alone (hit_base is 0 in every other render).
+    int32_t over;
+    int64_t hit_base;
 };
 
 // Blocks of k_trace_kd3's grid (fine tiles, split extras, far fill).
@@ -231,6 +237,10 @@ int launch_node_ref(const rt_kd_node* d_nodes, int64_t nnode, const int32_t* d_i
 int validate_leafs(const rt_leaf_aabb* leafs, uint32_t n, const char* what);
 int launch_unpack(int32_t w, int32_t h, int32_t nranks, const uint32_t* gathered,
                   uint32_t* frame, void* stream);
+// rt_render_clear: the miss state (background, hit -1, d = 400, zeros) into
+// the pixels a render of (nranks, rank, frame_out) addresses; hit may be null.
+int launch_clear(int32_t w, int32_t h, int32_t nranks, int32_t rank, bool frame_out, uint32_t* argb, int64_t* hit,
+                 float* aov, int64_t aov_stride, void* stream);
 // Slots s of `rank` whose band rank + s*nranks lies in [b0, b1): [s0, s1).
 __host__ __device__ inline void rect_slots(int32_t b0, int32_t b1, int32_t nranks, int32_t rank,
                                            int32_t& s0, int32_t& s1) {

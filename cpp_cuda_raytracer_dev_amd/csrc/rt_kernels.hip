@@ -97,6 +97,21 @@ int launch_unpack(int32_t w, int32_t h, int32_t nranks, const uint32_t* gathered
     return check_launch<void>("k_unpack");
 }
 
+int launch_clear(int32_t w, int32_t h, int32_t nranks, int32_t rank, bool frame_out, uint32_t* argb, int64_t* hit,
+                 float* aov, int64_t aov_stride, void* stream) {
+    const int32_t nbands = (h + kTileH - 1) / kTileH;
+    const int32_t slots = rank < nbands ? (nbands - rank + nranks - 1) / nranks : 0;
+    if (slots == 0 || w == 0) return RT_OK;
+    const bool vec = (w & 3) == 0 && (aov_stride & 3) == 0 && ((uintptr_t)argb & 15) == 0 && ((uintptr_t)hit & 15) == 0 &&
+                     ((uintptr_t)aov & 15) == 0;
+    const int32_t per_row = vec ? (w >> 2) : w;
+    const int64_t n = (int64_t)slots * kTileH * per_row;
+    const unsigned grid = (unsigned)std::min<int64_t>((n + 255) / 256, 8192);
+    (vec ? k_clear<4> : k_clear<1>)<<<grid, 256, 0, (hipStream_t)stream>>>(w, h, nranks, rank, frame_out ? 1 : 0, slots,
+                                                                          per_row, argb, hit, aov, aov_stride);
+    return check_launch<void>("k_clear");
+}
+
 int launch_pack_rect(int32_t w, int32_t h, int32_t nranks, int32_t rank, const int32_t rect[4],
                      const uint32_t* local, uint32_t* out, void* stream) {
     int32_t s0, s1;

@@ -148,6 +148,22 @@ __device__ __forceinline__ void put_miss(const TraceParams& P, int64_t out) {
     if (P.aov) put_aov_miss(P, out);
 }
 
+// rt_render_over (P.over, a wave-uniform test in the write-hit instances
+// only): a pixel is written iff it is a hit whose w is below the d now in
+// plane 0, the strict float compare of the reference's w < d
+// (TD/Trixel.cu:127), so a tie and a NaN keep what is there; every other
+// pixel gets no store at all.  over_d0 is the one-dword load of that d, for
+// a writer's entry (its latency hides behind the shading; coalesced like the
+// plane stores, a 32-byte run per 8-pixel row); the background writers skip
+// their stores under P.over.  All of it sits under `if constexpr (kWriteHit)`,
+// so the other instances compile from the statements they always had.
+__device__ __forceinline__ float over_d0(const TraceParams& P, int64_t out, bool hit) {
+    return P.over && hit ? P.aov[out] : 0.0f;
+}
+__device__ __forceinline__ bool over_keeps(const TraceParams& P, bool hit, float w, float d0) {
+    return P.over && !(hit && w < d0);
+}
+
 // Block -> tile.  Order 0: blocks b and b+8 share an XCD, so give each XCD a
 // contiguous run of tiles (bijective for any grid size); order 1: natural
 // (neighbouring tiles on different XCDs); order 2: the host's centre-out
@@ -339,7 +355,7 @@ __device__ __forceinline__ void kd_hit_values(const TraceParams& P, const Ray& R
 // A KD pixel's hit index in a write-hit instance, and its planes
 // (RT_FLAG_WRITE_AOV): the primary hit's, whatever a shadow ray found.
 __device__ __forceinline__ void put_hit_kd(const TraceParams& P, int64_t out, const Ray& R, float d, uint32_t best) {
-    P.hit[out] = best == kMiss ? (int64_t)-1 : (int64_t)best;
+    P.hit[out] = best == kMiss ? (int64_t)-1 : P.hit_base + (int64_t)best;
     if (!P.aov) return;
     if (best == kMiss) return put_aov_miss(P, out);
     float pnt[3], nrm[3], rad[3];
@@ -663,6 +679,8 @@ __global__ __launch_bounds__(kTileWKd * kTileH) void k_trace_kd2(TraceParams P) 
         ref = s_ref[k]; cmax = s_t0[k]; cmin = s_t1[k];
     }
 
+    [[maybe_unused]] float d0;
+    if constexpr (kWriteHit) d0 = over_d0(P, px.out, best != kMiss);
     uint32_t argb = kBackground;
     if (best != kMiss) {
         // kd_hit_values, spelled out as before it existed: through the helper
@@ -677,8 +695,12 @@ __global__ __launch_bounds__(kTileWKd * kTileH) void k_trace_kd2(TraceParams P) 
         const float rad[3] = {M.x, M.y, M.z};
         argb = phong(pnt, nrm, cam, rad);
     }
-    put_pixel(P, px.out, argb, best != kMiss);
-    if (kWriteHit) put_hit_kd(P, px.out, R, d, best);
+    if constexpr (!kWriteHit) {
+        put_pixel(P, px.out, argb, best != kMiss);
+    } else if (!over_keeps(P, best != kMiss, d, d0)) {
+        put_pixel(P, px.out, argb, best != kMiss);
+        put_hit_kd(P, px.out, R, d, best);
+    }
     if (kCount) {
         wave_count_add(&P.counters[0], n_int);
         wave_count_add(&P.counters[1], n_leaf);
@@ -2088,6 +2110,8 @@ template <bool kWriteHit, bool kCount>
 __device__ __forceinline__ void shade_out(const TraceParams& P, const Pixel& px, const Ray& R, const float cam[3],
                                           unsigned long long kbest, uint32_t best, bool shadowed, Counts& C) {
     const float d = __uint_as_float((uint32_t)(kbest >> 32));  // of a hit
+    [[maybe_unused]] float d0;
+    if constexpr (kWriteHit) d0 = over_d0(P, px.out, best != kMiss);
     uint32_t argb = kBackground;
     if (shadowed) {
         argb = 0x00000000u;  // point_rad stays 0: 0/0 -> (u8)NaN = 0 (H14)
@@ -2096,8 +2120,12 @@ __device__ __forceinline__ void shade_out(const TraceParams& P, const Pixel& px,
         kd_hit_values(P, R, d, best, pnt, nrm, rad);
         argb = phong(pnt, nrm, cam, rad);
     }
-    put_pixel(P, px.out, argb, best != kMiss);
-    if (kWriteHit) put_hit_kd(P, px.out, R, d, best);
+    if constexpr (!kWriteHit) {
+        put_pixel(P, px.out, argb, best != kMiss);
+    } else if (!over_keeps(P, best != kMiss, d, d0)) {
+        put_pixel(P, px.out, argb, best != kMiss);
+        put_hit_kd(P, px.out, R, d, best);
+    }
     if (kCount && best != kMiss) C.n_hit++;
 }
 
@@ -2500,8 +2528,12 @@ __device__ __forceinline__ bool fill_far(const TraceParams& P, const Unit& G, in
     const bool live = unit_pixel(P, G, 8, lane, px);
     if (!P.far_all && __ballot(live && ray_has_tiny_component(P, px.x, px.y)) != 0ull) return false;
     if (live) {
-        put_pixel(P, px.out, kBackground, false);
-        if (kWriteHit) put_miss(P, px.out);
+        if constexpr (!kWriteHit) {
+            put_pixel(P, px.out, kBackground, false);
+        } else if (!P.over) {
+            put_pixel(P, px.out, kBackground, false);
+            put_miss(P, px.out);
+        }
         if (kCount) C.n_int += 1u;  // the root visit, which fails
     }
     return true;
@@ -2512,8 +2544,12 @@ template <bool kWriteHit, bool kCount>
 __device__ __forceinline__ void fill_background(const TraceParams& P, const Unit& G, int lane, Counts& C) {
     Pixel px;
     if (unit_pixel(P, G, 8, lane, px)) {
-        put_pixel(P, px.out, kBackground, false);
-        if (kWriteHit) put_miss(P, px.out);
+        if constexpr (!kWriteHit) {
+            put_pixel(P, px.out, kBackground, false);
+        } else if (!P.over) {
+            put_pixel(P, px.out, kBackground, false);
+            put_miss(P, px.out);
+        }
         if (kCount) C.n_int += 1u;  // the root visit, which fails
     }
 }
@@ -2527,8 +2563,12 @@ __device__ __forceinline__ bool coarse_sure(const TraceParams& P, const Unit& G,
     const bool sure = !live || (P.plain_xf ? root_certain_miss(P, px.x, px.y) : root_certain_miss_xf(P, px.x, px.y));
     if (__ballot(!sure) != 0ull) return false;
     if (live) {
-        put_pixel(P, px.out, kBackground, false);
-        if (kWriteHit) put_miss(P, px.out);
+        if constexpr (!kWriteHit) {
+            put_pixel(P, px.out, kBackground, false);
+        } else if (!P.over) {
+            put_pixel(P, px.out, kBackground, false);
+            put_miss(P, px.out);
+        }
         if (kCount) C.n_int += 1u;  // the root visit, which fails
     }
     return true;
@@ -2548,8 +2588,12 @@ __device__ __forceinline__ unsigned long long coarse_root(const TraceParams& P, 
     constexpr unsigned long long kSub = (1ull << kRays) - 1;
     const bool traced = ((b >> ((lane / kRays) * kRays)) & kSub) != 0;
     if (live && !traced) {
-        put_pixel(P, px.out, kBackground, false);
-        if (kWriteHit) put_miss(P, px.out);
+        if constexpr (!kWriteHit) {
+            put_pixel(P, px.out, kBackground, false);
+        } else if (!P.over) {
+            put_pixel(P, px.out, kBackground, false);
+            put_miss(P, px.out);
+        }
         if (kCount) C.n_int += ni;  // the root visit; no root test passed in this sub-tile
     }
     return b;
@@ -2789,6 +2833,8 @@ struct FlatPair {
 template <bool kWriteHit>
 __device__ __forceinline__ void flat_shade_out(const TraceParams& P, const Pixel& px, const float rmd[3], float d,
                                                uint32_t best) {
+    [[maybe_unused]] float d0;
+    if constexpr (kWriteHit) d0 = over_d0(P, px.out, best != kMiss);
     uint32_t argb = kBackground;
     if (best != kMiss) {
         const float4 N = P.shade[2 * (size_t)best];
@@ -2797,12 +2843,16 @@ __device__ __forceinline__ void flat_shade_out(const TraceParams& P, const Pixel
         const float nrm[3] = {N.x, N.y, N.z};
         const float rad[3] = {M.x, M.y, M.z};
         argb = phong(pnt, nrm, rmd, rad);
-        if (kWriteHit && P.aov) put_aov(P, px.out, d, pnt, nrm, rad);
-    } else if (kWriteHit && P.aov) {
-        put_aov_miss(P, px.out);
+        if constexpr (kWriteHit) {
+            if (over_keeps(P, true, d, d0)) return;
+            if (P.aov) put_aov(P, px.out, d, pnt, nrm, rad);
+        }
+    } else if constexpr (kWriteHit) {
+        if (P.over) return;
+        if (P.aov) put_aov_miss(P, px.out);
     }
     put_pixel(P, px.out, argb, best != kMiss);
-    if (kWriteHit) P.hit[px.out] = best == kMiss ? (int64_t)-1 : (int64_t)best;
+    if (kWriteHit) P.hit[px.out] = best == kMiss ? (int64_t)-1 : P.hit_base + (int64_t)best;
 }
 
 // The flat list in one pass (RT_OPT_FLAT 9; counting renders): pair p + 1's
@@ -3085,6 +3135,41 @@ __global__ void k_unpack(int32_t w, int32_t h, int32_t nranks, int32_t slots, in
         if (i < (w >> 2)) reinterpret_cast<uint4*>(dst)[i] = reinterpret_cast<const uint4*>(src)[i];
     } else {
         for (int32_t k = i; k < w; k += gridDim.x * blockDim.x) dst[k] = src[k];
+    }
+}
+
+// rt_render_clear: the miss state into the rows a render of (nranks, rank,
+// frame_out) addresses -- band slot s of the rank holds frame rows (rank +
+// s*nranks)*8.., at packed rows s*8.. or, under frame_out, at their own.  A
+// grid-stride fill over `slots`*8 rows of `per_row` pieces of kVec pixels
+// (4: 16-byte stores, rows and planes 16-byte aligned; else word by word).
+template <int kVec>
+__global__ void k_clear(int32_t w, int32_t h, int32_t nranks, int32_t rank, int32_t frame_out, int32_t slots,
+                        int32_t per_row, uint32_t* __restrict__ argb, int64_t* __restrict__ hit,
+                        float* __restrict__ aov, int64_t stride) {
+    const int64_t n = (int64_t)slots * kTileH * per_row;
+    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) {
+        const int32_t row = (int32_t)(i / per_row), piece = (int32_t)(i - (int64_t)row * per_row);
+        const int32_t slot = row / kTileH, ly = row - slot * kTileH;
+        const int32_t band = rank + slot * nranks;
+        if (band * kTileH + ly >= h) continue;
+        const int64_t out = (int64_t)((frame_out ? band : slot) * kTileH + ly) * w + (int64_t)piece * kVec;
+        if (kVec == 4) {
+            *reinterpret_cast<uint4*>(argb + out) = make_uint4(kBackground, kBackground, kBackground, kBackground);
+            if (hit) {
+                const longlong2 m = make_longlong2(-1, -1);
+                *reinterpret_cast<longlong2*>(hit + out) = m;
+                *reinterpret_cast<longlong2*>(hit + out + 2) = m;
+            }
+            *reinterpret_cast<float4*>(aov + out) = make_float4(kDrawDistance, kDrawDistance, kDrawDistance, kDrawDistance);
+            for (int k = 1; k < RT_AOV_PLANES; k++)
+                *reinterpret_cast<float4*>(aov + k * stride + out) = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+        } else {
+            argb[out] = kBackground;
+            if (hit) hit[out] = (int64_t)-1;
+            aov[out] = kDrawDistance;
+            for (int k = 1; k < RT_AOV_PLANES; k++) aov[k * stride + out] = 0.0f;
+        }
     }
 }
 

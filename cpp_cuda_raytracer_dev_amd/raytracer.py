@@ -276,12 +276,18 @@ class Object:
         self.trixel_list = x
         self.quat = q if q is not None else Quaternion()
         self.motion = None  # set by Camera.add_object
+        self.hit_base = 0   # set by Camera.add_layer: added to this object's triangle indices in h_rmi
 
     def getTag(self) -> int:  # noqa: N802 (reference name)
         return self.object_tag
 
     def render(self, c: "Camera", mode: int = RT_MODE_KD, flags: int = 0, stream=None) -> int:
-        """Object::render (TD/Object.cpp:10-12)."""
+        """Object::render (TD/Object.cpp:10-12).  A layer object
+        (Camera.add_layer) renders over the frame already in the camera's
+        buffers (rt_render_over); the base object renders as ever."""
+        layer = c._layers.get(id(self))
+        if layer is not None:
+            return layer.render_over(None, None, self.quat.xform(), mode, flags, hit_base=self.hit_base, stream=stream)
         return self.trixel_list.intersect_trixels(c, self.quat, mode, flags, stream)
 
     def _moved(self) -> int:
@@ -310,6 +316,8 @@ class Camera:
 
     def __init__(self, r_w, r_h, f_w, f_h, fclen, p_x, p_y, p_z, la_x, la_y, la_z, up_x, up_y, up_z,
                  device: int = 0):
+        self._ctor = (r_w, r_h, f_w, f_h, fclen, p_x, p_y, p_z, la_x, la_y, la_z, up_x, up_y, up_z)
+        self._layers = {}  # id(layer object) -> its internal camera (add_layer), in render order
         self.res = (int(r_w), int(r_h))
         self.pos = np.array([p_x, p_y, p_z], np.float32)
         self.la = np.array([la_x, la_y, la_z], np.float32)
@@ -343,7 +351,42 @@ class Camera:
         _lib.call("rt_camera_add_object", self._h, new_object.trixel_list._h)
         return 0
 
+    def targets(self):
+        """rt_camera_targets: the camera's own device buffers as raw pointers
+        (argb, hit, planes) and the planes' stride."""
+        a, h, v, st = C.c_void_p(), C.c_void_p(), C.c_void_p(), C.c_int64()
+        _lib.call("rt_camera_targets", self._h, C.byref(a), C.byref(h), C.byref(v), C.byref(st))
+        return a, h, v, st.value
+
+    def add_layer(self, new_object: Object) -> int:
+        """A further object in this camera's frame (the reference's second
+        ``add_object``, whose render it leaves commented out,
+        TD/WinMain.cpp:152-156, :214-215): an internal camera of the same pose
+        on this camera's buffers.  ``new_object.render(cam)`` then draws the
+        object over what is there, nearest hit first (rt_render_over), with
+        ``new_object.hit_base`` added to its triangle indices: the triangle
+        counts of the base object and the earlier layers.  The base object's
+        renders keep the hit index and the planes from here on."""
+        if new_object.getTag() != TRIXEL_OBJECT_TAG:
+            return 0
+        if not self.object_list:
+            raise _lib.RtError("Camera.add_layer", -5, "add the base object (add_object) first")
+        layer = Camera(*self._ctor, device=self.device)
+        layer.cam_speed = self.cam_speed
+        layer.add_object(new_object)
+        for key, value in getattr(self, "_options", {}).items():
+            layer.set_option(key, value)
+        _, _, planes, stride = self.targets()
+        layer.set_aov(planes, stride)
+        layer._targets = self.targets()[:2]
+        new_object.hit_base = self.object_list[-1].trixel_list.num_trixels + sum(
+            c.object_list[-1].trixel_list.num_trixels for c in self._layers.values())
+        self._layers[id(new_object)] = layer
+        return 0
+
     def _render(self, t: Trixel, q, mode, flags, stream) -> int:
+        if self._layers:
+            flags |= RT_FLAG_WRITE_HIT | RT_FLAG_WRITE_AOV
         xf = (q if q is not None else Quaternion()).xform()
         s = C.c_void_p(stream) if isinstance(stream, int) else C.c_void_p(None)
         _lib.call("rt_render", self._h, _lib.ptr(xf), mode, flags, None, s)
@@ -390,6 +433,33 @@ class Camera:
         _lib.call("rt_render_into", self._h, _lib.ptr(xf), mode, flags, t, a, h, s)
         return 0
 
+    def render_over(self, argb, hit=None, xform=None, mode=RT_MODE_KD, flags=0, tile=None, hit_base=0,
+                    stream=None) -> int:
+        """rt_render_over: render over the frame already in the targets (argb /
+        hit: torch tensors or raw pointers, None = the camera's own; planes:
+        ``set_aov`` or the camera's own): a pixel is written only where this
+        object's nearest hit is nearer than the depth there."""
+        own = getattr(self, "_targets", (None, None))  # a layer camera: its base's buffers
+        if argb is None:
+            argb, hit = own[0], own[1] if hit is None else hit
+        xf = np.ascontiguousarray(xform if xform is not None else Quaternion().xform(), np.float32)
+        t = None if tile is None else C.byref(_lib.RtTile(tile[0], tile[1]))
+        s = C.c_void_p(stream) if isinstance(stream, int) else C.c_void_p(None)
+        a = argb if isinstance(argb, C.c_void_p) else _lib.ptr(argb)
+        h = hit if isinstance(hit, C.c_void_p) else _lib.ptr(hit)
+        _lib.call("rt_render_over", self._h, _lib.ptr(xf), mode, flags, t, a, h, int(hit_base), s)
+        return 0
+
+    def clear_layers(self, argb=None, hit=None, flags=0, tile=None, stream=None) -> int:
+        """rt_render_clear: the miss state (background, hit -1, d = 400, zeros)
+        into the targets, the order-free start of a composite."""
+        t = None if tile is None else C.byref(_lib.RtTile(tile[0], tile[1]))
+        s = C.c_void_p(stream) if isinstance(stream, int) else C.c_void_p(None)
+        a = argb if isinstance(argb, C.c_void_p) else _lib.ptr(argb)
+        h = hit if isinstance(hit, C.c_void_p) else _lib.ptr(hit)
+        _lib.call("rt_render_clear", self._h, flags, t, a, h, s)
+        return 0
+
     def render_display(self, clean, display, hit=None, xform=None, mode=RT_MODE_KD, flags=0, tile=None,
                        stream=None) -> int:
         """rt_render_display: the frame the reference's window shows
@@ -415,6 +485,9 @@ class Camera:
     def set_option(self, key: int, value: int) -> None:
         """Tuning knobs (_lib.RT_OPT_KERNEL, _lib.RT_OPT_TILE_ORDER); frames are identical."""
         _lib.call("rt_camera_set_option", self._h, key, value)
+        self._options = {**getattr(self, "_options", {}), key: value}
+        for layer in self._layers.values():  # the layers' cameras follow the base
+            layer.set_option(key, value)
 
     def get_option(self, key: int) -> int:
         v = C.c_int32()
@@ -439,6 +512,8 @@ class Camera:
         return self.h_color.reshape(h, w)
 
     def close(self):
+        for layer in getattr(self, "_layers", {}).values():
+            layer.close()
         if getattr(self, "_h", None) and self._h.value:
             _lib.lib().rt_camera_destroy(self._h)
             self._h = C.c_void_p()

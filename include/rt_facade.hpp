@@ -139,6 +139,9 @@ class Object {
 public:
     Trixel* trixel_list = nullptr;
     Quaternion* quat = nullptr;
+    // Camera::add_layer: added to this object's triangle indices in h_rmi
+    // (the triangle counts of the base object and the earlier layers)
+    s64 hit_base = 0;
 
     explicit Object(Trixel* x) : trixel_list(x), quat(&own_) {}
     Object(Trixel* x, Quaternion* q) : trixel_list(x), quat(&own_), own_(*q) {}
@@ -146,8 +149,9 @@ public:
     Object(const Object&) = delete;
     Object& operator=(const Object&) = delete;
     u8 getTag() const { return trixel_list->object_tag; }
-    // Object::render (TD/Object.cpp:10-12)
-    int render(Camera* c, u32 mode = RENDER_MODE_KD) { return trixel_list->intersect_trixels(c, quat, mode); }
+    // Object::render (TD/Object.cpp:10-12); a layer object (Camera::add_layer)
+    // renders over the frame already in the camera's buffers
+    inline int render(Camera* c, u32 mode = RENDER_MODE_KD);
     // Object::transform (TD/Object.cpp:14-17): needs Camera::add_object first
     int transform(Input* dq, u8 transform_select) {
         if (!motion_) return RT_ERR_STATE;
@@ -202,6 +206,10 @@ public:
         const float pos[3] = {p_x, p_y, p_z}, la[3] = {la_x, la_y, la_z}, up[3] = {up_x, up_y, up_z};
         status = rt_camera_create(dev, r_w, r_h, f_w, f_h, fclen, pos, la, up, &cam_);
         memcpy(pos_, pos, sizeof pos_);
+        memcpy(la_, la, sizeof la_);
+        memcpy(up_, up, sizeof up_);
+        film_[0] = f_w; film_[1] = f_h; film_[2] = fclen;
+        dev_ = dev;
         rt_camera_basis_t b;
         if (status == RT_OK) status = rt_camera_basis(r_w, r_h, f_w, f_h, fclen, pos, la, up, &b);
         if (status == RT_OK) {
@@ -213,7 +221,10 @@ public:
         h_mem.h_color.c = color_.data();
         h_mem.h_rmi.index = rmi_.data();
     }
-    ~Camera() { rt_camera_destroy(cam_); }
+    ~Camera() {
+        for (auto& l : layers_) rt_camera_destroy(l.cam);
+        rt_camera_destroy(cam_);
+    }
     Camera(const Camera&) = delete;
     Camera& operator=(const Camera&) = delete;
 
@@ -223,6 +234,54 @@ public:
         objects_.push_back(new_object);
         int rc = new_object->attach_motion(pos_, n_, u_, cam_speed);
         return rc ? rc : rt_camera_add_object(cam_, new_object->trixel_list->handle());
+    }
+
+    // A further object in this camera's frame: what the reference's second
+    // add_object is for (TD/WinMain.cpp:152-156; it leaves that object's
+    // render commented out, :214-215).  An internal camera with this one's
+    // constructor arguments, bound to this camera's buffers; new_object->
+    // render(this) then draws the object over what is there, nearest hit
+    // first (rt_render_over), so the reference's loop works as written:
+    // obj1->render; obj2->render; color_pixels.  Turns the hit buffer and
+    // write_pixel_memory on: the base object's render leaves the depths the
+    // layers are tested against.
+    int add_layer(Object* new_object) {
+        if (new_object->getTag() != TRIXEL_OBJECT_TAG) return 0;
+        if (objects_.empty()) return RT_ERR_STATE;  // add_object the base first
+        Layer l{new_object, nullptr};
+        int rc = rt_camera_create(dev_, (s32)f_prop.res.w, (s32)f_prop.res.h, film_[0], film_[1], film_[2], pos_, la_, up_,
+                                  &l.cam);
+        if (rc) return rc;
+        layers_.push_back(l);  // owned from here on
+        float* planes = nullptr;
+        int64_t stride = 0;
+        if ((rc = new_object->attach_motion(pos_, n_, u_, cam_speed)) ||
+            (rc = rt_camera_add_object(l.cam, new_object->trixel_list->handle())) ||
+            (rc = rt_camera_targets(cam_, nullptr, nullptr, &planes, &stride)) ||
+            (rc = rt_camera_set_aov(l.cam, planes, stride)))
+            return rc;
+        s64 base = objects_.back()->trixel_list->num_trixels;
+        for (size_t k = 0; k + 1 < layers_.size(); k++) base += layers_[k].obj->trixel_list->num_trixels;
+        new_object->hit_base = base;
+        keep_hit_buffer(true);
+        write_pixel_memory(true);
+        return RT_OK;
+    }
+    // Object::render of a layer object; RT_ERR_STATE for any other
+    int render_layer(Object* o, u32 mode) {
+        u32* argb = nullptr;
+        s64* hit = nullptr;
+        for (auto& l : layers_)
+            if (l.obj == o) {
+                int rc = rt_camera_targets(cam_, &argb, (int64_t**)&hit, nullptr, nullptr);
+                return rc ? rc : rt_render_over(l.cam, o->quat->rot_m, mode, 0u, nullptr, argb, (int64_t*)hit, o->hit_base, nullptr);
+            }
+        return RT_ERR_STATE;
+    }
+    bool is_layer(const Object* o) const {
+        for (auto& l : layers_)
+            if (l.obj == o) return true;
+        return false;
     }
 
     // Camera::color_pixels (TD/Camera.cpp:229): the frame to h_mem.h_color.c
@@ -256,7 +315,11 @@ public:
 
 private:
     rt_camera* cam_ = nullptr;
+    struct Layer { Object* obj; rt_camera* cam; };
+    std::vector<Layer> layers_;  // add_layer: the further objects and their cameras, in render order
     float pos_[3] = {0, 0, 0}, n_[3] = {0, 0, 1}, u_[3] = {1, 0, 0};
+    float la_[3] = {0, 0, 0}, up_[3] = {0, 1, 0}, film_[3] = {0, 0, 0};  // the constructor's arguments, for layers
+    int dev_ = 0;
     std::vector<u32> color_;
     std::vector<s64> rmi_;
     std::vector<Object*> objects_;
@@ -265,6 +328,9 @@ private:
 };
 
 inline int Trixel::intersect_trixels(Camera* c, Quaternion* q, u32 m) { return c->render_with(q, m); }
+inline int Object::render(Camera* c, u32 mode) {
+    return c->is_layer(this) ? c->render_layer(this, mode) : trixel_list->intersect_trixels(c, quat, mode);
+}
 
 // WinMain's film width ((float)w / h) * .024f (TD/WinMain.cpp:29,69-70).
 inline T_fp film_w(s32 w, s32 h) { return rt_film_w(w, h); }

@@ -232,6 +232,60 @@ int rt_render_into(rt_camera* c, const float* xform, uint32_t mode, uint32_t fla
 int rt_render_display(rt_camera* c, const float* xform, uint32_t mode, uint32_t flags, const rt_tile* tile,
                       uint32_t* d_clean, uint32_t* d_display, int64_t* d_hit, void* stream);
 
+/* Depth-tested renders: several objects composited into one frame.  One
+ * camera per object, all at the same pose, sharing target buffers (frame and
+ * hit through d_argb / d_hit, planes through rt_camera_set_aov; cameras may
+ * share one rt_scene).
+ *
+ * rt_render_over renders like rt_render_into with RT_FLAG_WRITE_HIT |
+ * RT_FLAG_WRITE_AOV implied, except in how a pixel is written.  With w this
+ * render's nearest-hit distance at a pixel and d0 the value now in plane 0 of
+ * the camera's plane target (bound or own), the pixel is written iff it is a
+ * hit and w < d0: a float compare, strict as the reference's w < d
+ * (TD/Trixel.cu:127), so a tie keeps what is there and so does a NaN d0.  A
+ * written pixel gets its colour (Phong, or 0x00000000 where RT_FLAG_SHADOW
+ * finds an occluder in this object), hit = hit_base + triangle, and all ten
+ * planes exactly as a plain RT_FLAG_WRITE_AOV render writes them.  Every
+ * other pixel -- a miss, the background everywhere, a hit that loses -- gets
+ * no store at all to the frame, the hit buffer or the planes.  Traversal,
+ * counters (RT_FLAG_COUNT) and cost orders are those of the plain render: the
+ * test is the last thing a pixel's writer does.
+ * d_argb / d_hit NULL: the camera's own frame / hit buffers; d_hit NULL with
+ * d_argb given: no hit index is kept.  Flags: RT_FLAG_COUNT, RT_FLAG_SHADOW,
+ * RT_FLAG_FRAME_OUT and the two implied ones; any other, or hit_base < 0,
+ * returns RT_ERR_INVALID.  Every mode, KD kernel, rays setting, tile and
+ * transform takes it, with RT_FLAG_WRITE_AOV's index rule.  When the target is
+ * the camera's own planes and no render or rt_render_clear has filled them:
+ * RT_ERR_STATE.  A bound stride below the pixels addressed: RT_ERR_INVALID.
+ * Nothing is launched on an error.  rt_render_display and rt_run_frames have
+ * no such variant.
+ *
+ * Our definition (the reference builds a second object, TD/WinMain.cpp:152-
+ * 156, but its render is commented out, :214-215, so it has no working second
+ * object to match): the compared quantity is the stored ray parameter
+ * d_dist.d; objects do not shadow one another; rt_comm_gather_frame's
+ * rectangle is one object's, so a multi-GPU composite gathers whole packed
+ * buffers and assembles them with rt_unpack_bands. */
+int rt_render_over(rt_camera* c, const float* xform, uint32_t mode, uint32_t flags, const rt_tile* tile,
+                   uint32_t* d_argb, int64_t* d_hit, int64_t hit_base, void* stream);
+
+/* The miss state into the same targets, for the pixels a render with that
+ * tile and RT_FLAG_FRAME_OUT setting (the only flag accepted) addresses: argb
+ * 0x00F08200, hit -1 (when there is a hit target), d = 400.0f and zeros in
+ * planes 1-9.  Marks the camera's own planes as filled.  Clear, then
+ * rt_render_over for every object, builds a frame in any object order; a
+ * plain RT_FLAG_WRITE_AOV render of the first object, then rt_render_over
+ * for the rest, is cheaper (its fused far fill is the clear). */
+int rt_render_clear(rt_camera* c, uint32_t flags, const rt_tile* tile, uint32_t* d_argb, int64_t* d_hit,
+                    void* stream);
+
+/* The camera's own device buffers: frame (w*h u32), hit (w*h int64), planes
+ * (RT_AOV_PLANES * plane_stride floats; allocated here if no render has yet,
+ * which alone does not make rt_read_aov succeed).  Any out pointer may be
+ * NULL.  For pointing a layer's camera at a base camera's buffers, whose
+ * rt_read_frame / rt_read_aov then read the composite. */
+int rt_camera_targets(rt_camera* c, uint32_t** d_argb, int64_t** d_hit, float** d_aov, int64_t* plane_stride);
+
 /* Pixels in one rank's packed buffer (uniform across ranks). */
 int64_t rt_tile_packed_pixels(int32_t w, int32_t h, int32_t nranks);
 

@@ -1,7 +1,7 @@
 // rt_headless.cpp -- the headless frame loop that replaces WinMain
 // (TD/WinMain.cpp:44-249), written against the reference-shaped C++ facade.
 //
-//   rt_headless <mesh.ply> <mode 0|1|2> [w h frames out.ppm flat keys] [--aov planes.f32]
+//   rt_headless <mesh.ply> <mode 0|1|2> [w h frames out.ppm flat keys] [--aov planes.f32] [--over KEYS]
 //
 // keys: held keys per frame, cycled, one input tick per frame (WinMain ticks
 // at TICK_RATE, :173): letters of R W S Q E T, '+' joins keys held together,
@@ -21,6 +21,24 @@
 
 using namespace rtmi;
 
+// "WWR+W.Q" -> held-key masks, one per tick
+static std::vector<uint32_t> parse_keys(const char* keys) {
+    std::vector<uint32_t> ticks;
+    uint32_t m = 0;
+    for (const char* k = keys;; k++) {
+        const char c = *k;
+        if (c == '+') continue;
+        m |= c == 'R' ? RT_KEY_R : c == 'W' ? RT_KEY_W : c == 'S' ? RT_KEY_S : c == 'Q' ? RT_KEY_Q
+           : c == 'E' ? RT_KEY_E : c == 'T' ? RT_KEY_T : 0u;
+        if (c == '\0' || k[1] != '+') {
+            if (c != '\0' || m) ticks.push_back(m);
+            m = 0;
+        }
+        if (c == '\0') break;
+    }
+    return ticks;
+}
+
 static double now_s() {
     return std::chrono::duration<double>(std::chrono::steady_clock::now().time_since_epoch()).count();
 }
@@ -29,16 +47,22 @@ int main(int argc, char** argv) {
     // --aov FILE (anywhere on the line): also keep the per-pixel hit results
     // (Camera::write_pixel_memory) and write the last frame's ten planes
     // (d, pnt.xyz, norm.xyz, rad.rgb; w*h floats each, row 0 = bottom) as raw float32
+    // --over KEYS (anywhere on the line): the second object, which WinMain
+    // builds and never renders (:152-156, :214-215), is a layer of the frame
+    // (Camera::add_layer): the same mesh posed by these key ticks, applied
+    // once, and rendered over the first object every frame
     const char* aov_out = nullptr;
-    for (int k = 1; k + 1 < argc; k++)
-        if (!std::strcmp(argv[k], "--aov")) {
-            aov_out = argv[k + 1];
-            for (int j = k; j + 2 < argc; j++) argv[j] = argv[j + 2];
-            argc -= 2;
-            break;
-        }
+    const char* over_keys = nullptr;
+    for (int k = 1; k + 1 < argc;) {
+        const bool aov = !std::strcmp(argv[k], "--aov"), over = !std::strcmp(argv[k], "--over");
+        if (!aov && !over) { k++; continue; }
+        (aov ? aov_out : over_keys) = argv[k + 1];
+        for (int j = k; j + 2 < argc; j++) argv[j] = argv[j + 2];
+        argc -= 2;
+    }
     if (argc < 3) {
-        std::fprintf(stderr, "usage: %s mesh.ply mode [w h frames out.ppm flat keys] [--aov planes.f32]\n", argv[0]);
+        std::fprintf(stderr, "usage: %s mesh.ply mode [w h frames out.ppm flat keys] [--aov planes.f32] [--over KEYS]\n",
+                     argv[0]);
         return 2;
     }
     const char* mesh = argv[1];
@@ -48,20 +72,7 @@ int main(int argc, char** argv) {
     const char* out = argc > 6 ? argv[6] : nullptr;
     const u32 render_mode = (argc > 7 && std::atoi(argv[7])) ? RENDER_MODE_FLAT : RENDER_MODE_KD;
     std::vector<uint32_t> ticks;  // held-key masks, one per frame
-    if (argc > 8) {
-        uint32_t m = 0;
-        for (const char* k = argv[8];; k++) {
-            const char c = *k;
-            if (c == '+') continue;
-            m |= c == 'R' ? RT_KEY_R : c == 'W' ? RT_KEY_W : c == 'S' ? RT_KEY_S : c == 'Q' ? RT_KEY_Q
-               : c == 'E' ? RT_KEY_E : c == 'T' ? RT_KEY_T : 0u;
-            if (c == '\0' || k[1] != '+') {
-                if (c != '\0' || m) ticks.push_back(m);
-                m = 0;
-            }
-            if (c == '\0') break;
-        }
-    }
+    if (argc > 8) ticks = parse_keys(argv[8]);
 
     Camera* main_cam = new Camera(w, h, film_w(w, h), (T_fp).024, (T_fp).055, (T_fp)0.0, (T_fp)0.10, (T_fp)-1.0,
                                   (T_fp)0.00, (T_fp)0.100, (T_fp)0.00, (T_fp)0.0, (T_fp)1.0, (T_fp)0.0);
@@ -94,10 +105,13 @@ int main(int argc, char** argv) {
 
     Object* obj1 = new Object(trixel_list);
     Object* obj2 = new Object(trixel_list);
-    if (main_cam->add_object(obj1) || main_cam->add_object(obj2)) {
+    if (main_cam->add_object(obj1) || (over_keys ? main_cam->add_layer(obj2) : main_cam->add_object(obj2))) {
         std::fprintf(stderr, "add_object: %s\n", rt_last_error_string());
         return 1;
     }
+    if (over_keys)
+        for (uint32_t m : parse_keys(over_keys))
+            if (obj2->key_tick(m)) { std::fprintf(stderr, "transform: %s\n", rt_last_error_string()); return 1; }
 
     // warm up, then time `frames` frames of render + D2H (the reference's FPS loop)
     obj1->render(main_cam, render_mode);
@@ -108,7 +122,10 @@ int main(int argc, char** argv) {
             std::fprintf(stderr, "transform: %s\n", rt_last_error_string());
             return 1;
         }
-        if (obj1->render(main_cam, render_mode)) { std::fprintf(stderr, "render: %s\n", rt_last_error_string()); return 1; }
+        if (obj1->render(main_cam, render_mode) || (over_keys && obj2->render(main_cam, render_mode))) {
+            std::fprintf(stderr, "render: %s\n", rt_last_error_string());
+            return 1;
+        }
         if (main_cam->color_pixels(PHONG_COLOR_TAG)) {
             std::fprintf(stderr, "color_pixels: %s\n", rt_last_error_string());
             return 1;
