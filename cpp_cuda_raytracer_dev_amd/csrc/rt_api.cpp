@@ -85,6 +85,8 @@ struct rt_camera {
     uint64_t prepared_version = 0;
     float4* d_trec = nullptr;        // camera-relative triangle records
     float4* d_inode = nullptr;       // camera-relative interior nodes
+    float2* d_split = nullptr;       // a tree with kCamSplitFields: its s1 / s2 fields per interior record
+    int64_t split_cap = 0;
     int32_t* d_cam_flags = nullptr;  // k_cam_nodes' flags (kCamTinyS1, kCamUnordered) ...
     int32_t cam_flags = kCamUnordered;  // ... read back once the records are built
     float4* d_tpair = nullptr;       // flat variant 2: camera-relative triangle pairs
@@ -309,7 +311,7 @@ int prepare_camera_object(rt_camera* c) {
         // init_camera_voxel_device_memory (TD/Camera.cu:163-187)
         if ((rc = hip_check(hipMemset(c->d_cam_flags, 0, sizeof(int32_t)), "memset cam flags")) ||
             (rc = launch_cam_nodes(s->d_nodes, s->d_interior_ids, s->d_node_ref, s->ninterior, c->pos,
-                                   c->d_inode, c->d_cam_flags, nullptr)))
+                                   c->d_inode, c->d_cam_flags, nullptr, nullptr)))
             return rc;
     }
     if ((rc = hip_check(hipDeviceSynchronize(), "camera object prep"))) return rc;
@@ -317,6 +319,21 @@ int prepare_camera_object(rt_camera* c) {
     if (s->d_nodes && s->ninterior > 0 &&
         (rc = hip_check(hipMemcpy(&c->cam_flags, c->d_cam_flags, sizeof(int32_t), hipMemcpyDeviceToHost), "D2H cam flags")))
         return rc;
+    if (c->cam_flags & kCamSplitFields) {
+        // the fields of a tree whose split planes are not its boxes' bounds: a
+        // second pass writes them beside the records (TraceParams::split_planes)
+        if (c->split_cap < s->ninterior) {
+            dev_free(c->d_split);
+            c->d_split = nullptr;
+            c->split_cap = 0;
+            if ((rc = dev_alloc(&c->d_split, (size_t)s->ninterior, "hipMalloc(split planes)"))) return rc;
+            c->split_cap = s->ninterior;
+        }
+        if ((rc = launch_cam_nodes(s->d_nodes, s->d_interior_ids, s->d_node_ref, s->ninterior, c->pos, c->d_inode,
+                                   c->d_cam_flags, c->d_split, nullptr)) ||
+            (rc = hip_check(hipDeviceSynchronize(), "camera split planes")))
+            return rc;
+    }
     c->geom_gen++;  // cached launch parameters carry the flags
     // kept cost orders measured another object or tree: a grid
     // of the same key must not restart from them (the camera's position is
@@ -1319,6 +1336,7 @@ int fill_params(rt_camera* c, const float* xform, const rt_tile* tile, uint32_t*
                 uint32_t mode, TraceParams& p, hipStream_t st) {
     const rt_scene* s = c->obj;
     p.inode = c->d_inode;
+    p.split_planes = (c->cam_flags & kCamSplitFields) ? c->d_split : nullptr;
     p.trec = c->d_trec;
     p.leaf_off = c->leaf_off;
     p.rec_bytes = c->leaf_off ? (uint32_t)(c->leaf_off + 64 * (uint64_t)c->obj->ntri) : 0u;
@@ -2407,6 +2425,7 @@ extern "C" void rt_camera_destroy(rt_camera* c) {
     dev_free(c->d_counters);
     dev_free(c->d_err);
     dev_free(c->d_cam_flags);
+    dev_free(c->d_split);
     dev_free(c->d_rec);
     dev_free(c->d_tpair);
     for (auto& o : c->oslot) {

@@ -42,7 +42,7 @@ constexpr uint32_t kRefMask = 0x1FFFFFFFu;
 constexpr uint32_t kAxisShift = 29;
 constexpr uint32_t kTinyS1Bit = 1u << 29;
 // k_cam_nodes' flags of a camera's records
-constexpr int32_t kCamTinyS1 = 1, kCamUnordered = 2;
+constexpr int32_t kCamTinyS1 = 1, kCamUnordered = 2, kCamSplitFields = 4;
 
 // rt_camera_set_option keys.
 enum Option : int32_t {
@@ -193,6 +193,12 @@ struct TraceParams {
     // the write-hit instances alone (hit_base is 0 in every other render).
     int32_t over;
     int64_t hit_base;
+    // A tree whose s1 / s2 fields are not its children's bounds on the cut
+    // axis (k_cam_nodes' kCamSplitFields; no builder makes one): the fields,
+    // camera-relative, per interior record, for the walks that otherwise read
+    // the split planes from the record's child boxes; null for every other
+    // tree.  Last for the same reason as the planes.
+    const float2* split_planes;
 };
 
 // Blocks of k_trace_kd3's grid (fine tiles, split extras, far fill).
@@ -211,7 +217,7 @@ int launch_cam_tri(const float4* tri_world, uint32_t ntri, const float pos[3],
 int launch_pair_tri(const float4* trec, uint32_t ntri, float4* tpair, void* stream);
 int launch_cam_nodes(const rt_kd_node* nodes, const int32_t* interior_ids,
                      const uint32_t* node_ref, int64_t ninterior, const float pos[3],
-                     float4* inode, int32_t* flags, void* stream);
+                     float4* inode, int32_t* flags, float2* split_planes, void* stream);
 // part: the coarse groups then the fine tiles (kPartAll), or one of them.
 enum LaunchPart : int { kPartAll = 0, kPartFine = 1, kPartCoarse = 2 };
 int launch_trace(const TraceParams& p, uint32_t mode, uint32_t flags, int kernel_version,

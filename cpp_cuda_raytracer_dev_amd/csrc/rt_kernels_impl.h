@@ -618,16 +618,20 @@ __global__ __launch_bounds__(kTileWKd * kTileH) void k_trace_kd2(TraceParams P) 
             const uint32_t L = lw & ~(3u << kAxisShift), Rr = __float_as_uint(r3.w) & ~kTinyS1Bit;
             const float dir = axis == 0 ? dir_a[0] : axis == 1 ? dir_a[1] : dir_a[2];
             const float mx = cmax * dir, mn = cmin * dir;
-            float s1;
+            float s1, s1r = rec_s1(r0, r1, axis), s2r = rec_s2(r1, r2, axis);
+            if (P.split_planes) {  // (a tree whose fields are not its boxes' bounds: TraceParams)
+                const float2 pl = P.split_planes[ref];
+                s1r = pl.x; s2r = pl.y;
+            }
             bool lt, gt;  // the reference's double tests against s2 (TD/Trixel.cu:155-157)
             if (kTranslated) {
                 const float ds = axis == 0 ? ds_a[0] : axis == 1 ? ds_a[1] : ds_a[2];
-                s1 = (float)((double)rec_s1(r0, r1, axis) + kEps + (double)ds);
-                const float s2 = rec_s2(r1, r2, axis) + ds;
+                s1 = (float)((double)s1r + kEps + (double)ds);
+                const float s2 = s2r + ds;
                 lt = pred::lt_eps(mx, s2);
                 gt = pred::gt_eps(mn, s2);
             } else {  // ds == 0: the record's exact float thresholds
-                s1 = pred::add_eps(rec_s1(r0, r1, axis));
+                s1 = pred::add_eps(s1r);
                 lt = mx < r3.y;
                 gt = mn > r3.x;
             }
@@ -1036,7 +1040,7 @@ template <bool kTranslated, bool kCount, bool kFast = false, bool kAny = false>
 __device__ __forceinline__ void order_node(const TraceParams& P, const Ray& Q, float4 q2, float4 q3, float4 q4,
                                            float t0, float t1, float4 r0, float4 r1, float4 r2, float4 r3, float lt0,
                                            float lt1, float rt0, float rt1, bool real, Order& o, uint32_t& n_int,
-                                           uint32_t& n_desc) {
+                                           uint32_t& n_desc, uint32_t rec = 0u) {
     const uint32_t lw = __float_as_uint(r3.z), rw = __float_as_uint(r3.w);
     const uint32_t axis = (lw >> kAxisShift) & 3u;
     const uint32_t L = lw & ~(3u << kAxisShift), Rr = rw & ~kTinyS1Bit;
@@ -1045,13 +1049,20 @@ __device__ __forceinline__ void order_node(const TraceParams& P, const Ray& Q, f
     // The reference's double-promoted epsilon tests (TD/Trixel.cu:146-157):
     // against s2 through the record's exact float thresholds (k_cam_nodes)
     // unless the object is translated
-    const float s1r = rec_s1(r0, r1, axis);
+    // rec: the record's index, for a tree whose split planes are not its
+    // boxes' bounds (TraceParams::split_planes; never under kFast); a lane
+    // whose item is a leaf reads record 0 and drops the result
+    float s1r = rec_s1(r0, r1, axis), s2r = rec_s2(r1, r2, axis);
+    if (!kFast && P.split_planes) {
+        const float2 pl = P.split_planes[(rec & kLeafBit) ? 0u : rec];
+        s1r = pl.x; s2r = pl.y;
+    }
     float s1;
     bool left_first, pa;
     if (kTranslated) {
         const float ds = axis == 0 ? q3.w : axis == 1 ? q4.x : q4.y;
         s1 = (float)((double)s1r + kEps + (double)ds);
-        const float s2 = rec_s2(r1, r2, axis) + ds;
+        const float s2 = s2r + ds;
         left_first = pred::lt_eps_ref(mx, s2);
         pa = pred::gt_eps_ref(mn, s2);
     } else {
@@ -1117,7 +1128,7 @@ __device__ __forceinline__ void visit_interior(const TraceParams& P, const Ray& 
     child_slabs<kFast>(Q, r0, r1, r2, lt0, lt1, rt0, rt1);
     Order od;
     order_node<kTranslated, kCount, kFast, kAny>(P, Q, q2, q3, q4, __uint_as_float(it.y), __uint_as_float(it.z), r0, r1, r2,
-                                           r3, lt0, lt1, rt0, rt1, true, od, n_int, n_desc);
+                                           r3, lt0, lt1, rt0, rt1, true, od, n_int, n_desc, it.x);
     const uint32_t meta_first = (ray << 26) | (marked << 1);
     const uint32_t meta_second = meta_first | 1u;
     o.ca = make_uint4(od.first, __float_as_uint(od.f0), __float_as_uint(od.f1), meta_first);
@@ -1561,7 +1572,7 @@ __device__ __forceinline__ int two_level_iter(const TraceParams& P, uint4* items
     const float t1 = role == 0 ? __uint_as_float(it.z) : role == 1 ? xl1 : xr1;
     Order o;
     order_node<kTranslated, kCount, kFast, kAny>(P, Q, q2, q3, q4, t0, t1, a0, a1, a2, a3, at0, at1, bt0, bt1, false, o, n_int,
-                                           n_desc);
+                                           n_desc, child ? 2u * it.x + (uint32_t)role : it.x);
     // role 0's verdict on its node's children, to roles 1 and 2
     const uint32_t fl = quad_bcast0((o.left_first ? 1u : 0u) | (o.ka ? 2u : 0u) | (o.kb ? 4u : 0u));
     const bool lfirst = (fl & 1u) != 0;
@@ -3090,7 +3101,8 @@ __device__ __forceinline__ float floor_f(double d) {
 // boxes inside the root's: rt_api.cpp fast_proof).
 __global__ void k_cam_nodes(const rt_kd_node* __restrict__ nodes, const int32_t* __restrict__ ids,
                             const uint32_t* __restrict__ node_ref, int64_t ninterior, float cx,
-                            float cy, float cz, float4* __restrict__ out, int32_t* __restrict__ flags) {
+                            float cy, float cz, float4* __restrict__ out, int32_t* __restrict__ flags,
+                            float2* __restrict__ split_planes) {
     const int64_t k = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (k >= ninterior) return;
     const rt_kd_node nd = nodes[ids[k]];
@@ -3113,7 +3125,17 @@ __global__ void k_cam_nodes(const rt_kd_node* __restrict__ nodes, const int32_t*
     for (int a = 0; a < 3; a++)
         ordered = ordered && lb[2 * a] <= lb[2 * a + 1] && rb[2 * a] <= rb[2 * a + 1] && lb[2 * a] >= pb[2 * a] &&
                   rb[2 * a] >= pb[2 * a] && lb[2 * a + 1] <= pb[2 * a + 1] && rb[2 * a + 1] <= pb[2 * a + 1];
-    const int32_t f = (tiny ? kCamTinyS1 : 0) | (ordered ? 0 : kCamUnordered);
+    // The walks read s1 / s2 from the child boxes (rec_s1 / rec_s2), the
+    // reference from the node's fields: create_kd makes them the same floats.
+    // A tree where they differ (rt_scene_set_kd accepts any) keeps the double
+    // forms (as an unordered one) and takes the fields from split_planes,
+    // which rt_api.cpp fills in a second pass over such a tree.
+    // (bit for bit: the walks then read the very floats the reference reads)
+    const bool fields = __float_as_uint(s1) == __float_as_uint(lb[2 * axis + 1]) &&
+                        __float_as_uint(s2) == __float_as_uint(rb[2 * axis]);
+    if (split_planes) split_planes[k] = make_float2(s1, s2);
+    const int32_t f = (tiny ? kCamTinyS1 : 0) | (ordered ? 0 : kCamUnordered) |
+                      (fields ? 0 : (kCamSplitFields | kCamUnordered));
     if (f) atomicOr(flags, f);
     out[4 * k + 3] = make_float4(s_gt, s_lt, __uint_as_float(node_ref[nd.left] | (axis << kAxisShift)),
                                  __uint_as_float(node_ref[nd.right] | tiny));

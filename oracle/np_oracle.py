@@ -193,11 +193,12 @@ def _mt_accept(u, v, w, d):
     return (w < d) and not ((D(u) < EPS) or (D(v) < EPS) or (D(F(u + v)) > D(1) + EPS) or (D(w) < EPS))
 
 
-def _walk(S, r, od, on_leaf, lim=None):
+def _walk(S, r, od, on_leaf, lim=None, cnt=None):
     """The DFS of intersect_voxel_cuda (TD/Trixel.cu:70-170) for direction r and
     translation od; on_leaf(t, u, v, w) sees every non-degenerate MT test.
     lim: a shadow segment's walk enters a box only below lim (oracle.c
-    trace_shadow)."""
+    trace_shadow).  cnt: a list [interior visits, leaf visits, accepts, hit
+    pixels, descents] that the walk adds its visits to (render(counters=True))."""
     inv = [F(F(1) / r[k]) for k in range(3)]
     o = [F(od[k] / r[k]) for k in range(3)]
     stack = [0]
@@ -205,6 +206,8 @@ def _walk(S, r, od, on_leaf, lim=None):
         cni = stack.pop()
         vx = S["vox"][cni]
         if vx["leaf"]:
+            if cnt is not None:
+                cnt[1] += 1
             t = vx["tri"]
             e1, e2, dt = S["e1"][t], S["e2"][t], S["dt"][t]
             p = cross(r, e2)
@@ -218,6 +221,8 @@ def _walk(S, r, od, on_leaf, lim=None):
                 w = F(pe1 * dot(e2, q))
                 on_leaf(t, u, v, w)
             continue
+        if cnt is not None:
+            cnt[0] += 1
         bo = vx["bo"]
         t0 = [F(bo[k] * inv[k]) if r[k] > 0 else F(bo[k + 3] * inv[k]) for k in range(3)]
         t1 = [F(bo[k + 3] * inv[k]) if r[k] > 0 else F(bo[k] * inv[k]) for k in range(3)]
@@ -227,6 +232,8 @@ def _walk(S, r, od, on_leaf, lim=None):
         maxt0 = np.fmax(F(t0[2] + o[2]), np.fmax(F(t0[0] + o[0]), F(t0[1] + o[1])))
         mint1 = np.fmin(F(t1[2] + o[2]), np.fmin(F(t1[0] + o[0]), F(t1[1] + o[1])))
         if D(mint1) >= D(maxt0) - EPS and D(maxt0) > -EPS and (lim is None or maxt0 < lim):
+            if cnt is not None:
+                cnt[4] += 1
             maxt0, mint1 = F(maxt0 * dr), F(mint1 * dr)
             s1 = F(D(vx["s1"]) + EPS + D(ds))
             s2 = F(vx["s2"] + ds)
@@ -240,7 +247,7 @@ def _walk(S, r, od, on_leaf, lim=None):
                 stack.append(vx["right"])
 
 
-def trace_kd(S, X, cam_rmd):
+def trace_kd(S, X, cam_rmd, cnt=None):
     """intersect_voxel_cuda, TD/Trixel.cu:41-172.  Returns (rmi, d, (pnt, nrm),
     (r, od)) -- the last pair is the object-space ray, for the shadow ray."""
     X = [F(x) for x in X]
@@ -251,6 +258,8 @@ def trace_kd(S, X, cam_rmd):
 
     def leaf(t, u, v, w):
         if _mt_accept(u, v, w, st["d"]):
+            if cnt is not None:
+                cnt[2] += 1
             st["d"], st["rmi"] = w, t
             pnt = [F(F(w * r[k]) + od[k]) for k in range(3)]
             n = S["nrm"][t]
@@ -259,14 +268,14 @@ def trace_kd(S, X, cam_rmd):
                   for k in range(3)]
             st["out"] = (pnt, nr)
 
-    _walk(S, r, od, leaf)
+    _walk(S, r, od, leaf, cnt=cnt)
     return st["rmi"], st["d"], st["out"], (r, od)
 
 
 SHADOW_SCALE = F(0.9990234375)  # 1 - 2^-10
 
 
-def trace_shadow(S, rmi, d, ray, segment=True):
+def trace_shadow(S, rmi, d, ray, segment=True, cnt=None):
     """The shadow segment of a hit (oracle.c trace_shadow): from the light
     (2,2,2) to H = d*r - od, walked from the light; True if occluded.
     segment=False: rounds 1-5's walk of the whole ray beyond H (tests only:
@@ -280,13 +289,15 @@ def trace_shadow(S, rmi, d, ray, segment=True):
 
     def leaf(t, u, v, w):
         if t != rmi and _mt_accept(u, v, w, lmax):
+            if cnt is not None:
+                cnt[2] += 1
             hit[0] = True
 
-    _walk(S, list(s), (F(-2), F(-2), F(-2)), leaf, lim=lmax if segment else None)
+    _walk(S, list(s), (F(-2), F(-2), F(-2)), leaf, lim=lmax if segment else None, cnt=cnt)
     return hit[0]
 
 
-def trace_flat(S, rmd):
+def trace_flat(S, rmd, cnt=None):
     """intersect_trixel_cuda, TD/Trixel.cu:173-209."""
     d, rmi, out = F(400.0), -1, None
     for t in range(len(S["e1"])):
@@ -298,8 +309,12 @@ def trace_flat(S, rmd):
             v = F(pe1 * dot(rmd, S["dq"][t]))
             w = F(pe1 * S["dw"][t])
             if _mt_accept(u, v, w, d):
+                if cnt is not None:
+                    cnt[2] += 1
                 d, rmi = w, t
                 out = ([F(d * rmd[k]) for k in range(3)], list(S["nrm"][t]))
+    if cnt is not None:
+        cnt[1] += len(S["e1"])
     return rmi, d, out
 
 
@@ -332,7 +347,10 @@ def phong(pnt, nrm, rmd, rad):
 RAD = (F(0.1), F(0.55), F(0.2))
 
 
-def render(points9, nodes, cam, mode=0, xform=None, shadow=False, segment=True):
+def render(points9, nodes, cam, mode=0, xform=None, shadow=False, segment=True, counters=False):
+    """-> (argb, hit); with counters=True also the five visit counters of
+    oracle.c (interior, leaf, accept, hit pixels, descend), counted here."""
+    cnt = [0, 0, 0, 0, 0] if counters else None
     S = prepare(points9, nodes if mode == 0 else None, cam)
     X = IDENT if xform is None else np.asarray(xform, F)
     w, h = cam["w"], cam["h"]
@@ -343,16 +361,28 @@ def render(points9, nodes, cam, mode=0, xform=None, shadow=False, segment=True):
             for ix in range(w):
                 rmd = primary_ray(cam, ix, iy)
                 if mode == 0:
-                    rmi, d, out, ray = trace_kd(S, X, rmd)
+                    rmi, d, out, ray = trace_kd(S, X, rmd, cnt)
                 else:
-                    rmi, d, out = trace_flat(S, rmd)
+                    rmi, d, out = trace_flat(S, rmd, cnt)
                 i = iy * w + ix
                 hit[i] = rmi
                 if rmi >= 0:
+                    if cnt is not None:
+                        cnt[3] += 1
                     argb[i] = phong(out[0], out[1], rmd, RAD)
-                    if shadow and trace_shadow(S, rmi, d, ray, segment):
+                    if shadow and trace_shadow(S, rmi, d, ray, segment, cnt):
                         argb[i] = 0
+    if counters:
+        return argb, hit, cnt
     return argb, hit
+
+
+def nodes_from_array(nodes):
+    """A KD node array (the oracle's NODE_DTYPE or the product's node dtype:
+    the same field names) as the node dicts prepare() takes."""
+    return [dict(x0=F(n["x0"]), x1=F(n["x1"]), y0=F(n["y0"]), y1=F(n["y1"]), z0=F(n["z0"]), z1=F(n["z1"]),
+                 s1=F(n["s1"]), s2=F(n["s2"]), cut=int(n["cut_flag"]), leaf=int(n["is_leaf"]),
+                 tri=int(n["tri_index"]), left=int(n["left"]), right=int(n["right"])) for n in nodes]
 
 
 def window_frames(frames, hits):

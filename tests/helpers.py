@@ -116,6 +116,17 @@ class GpuScene:
                 h.close()
 
 
+def rot_y(deg, t=(0.0, 0.0, 0.0)):
+    """rot_m rows of a rotation by `deg` about y and an offset t (float32)."""
+    a = np.deg2rad(deg)
+    c, s = np.float32(np.cos(a)), np.float32(np.sin(a))
+    return np.array([[c, 0, s, t[0]], [0, 1, 0, t[1]], [-s, 0, c, t[2]]], np.float32).reshape(12)
+
+
+#: a signed permutation (exact zeros in rot_m) with a small offset
+SIGNED_PERM = np.array([0, 0, 1, 0.01, 0, 1, 0, 0, -1, 0, 0, 0], np.float32)
+
+
 def golden():
     return np.load(GOLDEN, allow_pickle=False)
 

@@ -1,0 +1,416 @@
+"""Synthetic edge-case scenes for the parity tests: seeded generators and a
+scene pair that sends the same arrays through the product (HIP library) and
+through the oracle (C restatement; the numpy restatement as a second anchor).
+
+The mesh fixtures (tests/helpers.py) are natural models: no leaf root, no
+exact depth ties, no box bound of exactly zero, nothing near the reference's
+1e-16 thresholds.  The scenes here are built to have them.  The scene tables
+at the end are shared by tests/test_synth_cpu.py (which proves on the oracle
+alone that each scene has the property it is there for) and
+tests/test_gpu_synth.py (which compares the kernels with the oracle on them).
+"""
+import numpy as np
+
+from cpp_cuda_raytracer_dev_amd import raytracer as R
+from oracle import _oracle as O, np_oracle as N
+from tests import helpers as H
+
+F = np.float32
+
+
+# ------------------------------------------------------------------ cameras
+
+def default_cam(w, h):
+    """The WinMain camera at w x h with every field written out (scaled() needs f_w)."""
+    return dict(f_w=F(R.film_w(w, h)), f_h=F(.024), focal=F(.055), pos=(0.0, 0.1, -1.0), look_at=(0.0, 0.1, 0.0),
+                up=(0.0, 1.0, 0.0))
+
+
+# --------------------------------------------------------------- generators
+
+def soup(n, seed):
+    """n random triangles in front of the default camera: centres within
+    +-0.3 of (0, 0.1, 0), vertices within +-0.15 of their centre."""
+    rng = np.random.default_rng(seed)
+    c = rng.uniform(-0.3, 0.3, size=(n, 1, 3)) + np.array([0.0, 0.1, 0.0])
+    v = (c + rng.uniform(-0.15, 0.15, size=(n, 3, 3))).astype(F).reshape(3 * n, 3)
+    return v, np.arange(3 * n, dtype=np.int32).reshape(n, 3)
+
+
+def edge_soup(n, seed):
+    """A soup of n >= 12 triangles with the flat test's cases in it: both
+    windings, a zero-area triangle (5), one whose plane x = 0 holds the eye
+    (7), one behind the eye (9) and one that crosses the eye's depth (11).
+    The whole soup is folded above the eye's height (y >= 0.12): the
+    reference's walk enters no box that holds the eye, and with triangles
+    behind the eye the root box would hold it on every other axis."""
+    assert n >= 12
+    v, f = soup(n, seed)
+    f[1::2] = f[1::2, ::-1]                       # both windings
+    v[3 * 5 + 2] = v[3 * 5]                       # zero area (two equal vertices)
+    v[3 * 7:3 * 7 + 3, 0] = 0.0                   # plane x = 0 holds the default eye
+    v[3 * 9:3 * 9 + 3, 2] -= F(1.5)               # behind the eye (z < -1)
+    v[3 * 11, 2] = F(-1.3)                        # one vertex behind the eye, two in front
+    v[:, 1] = F(0.12) + F(0.6) * np.abs(v[:, 1] - F(0.1))
+    return v, f
+
+
+def copies(n, k, seed):
+    """soup(n) with every triangle k times, vertex bits identical, the k * n
+    triangles in a seeded random order: copies tie exactly in depth, and the
+    lowest index among them (the flat list's winner) is not in general the
+    copy the KD walk visits first."""
+    v, _ = soup(n, seed)
+    tri = np.tile(v.reshape(n, 3, 3), (k, 1, 1))
+    perm = np.random.default_rng(seed + 1).permutation(k * n)
+    v = np.ascontiguousarray(tri[perm].reshape(3 * k * n, 3))
+    return v, np.arange(3 * k * n, dtype=np.int32).reshape(k * n, 3)
+
+
+def grid():
+    """Axis-aligned quads (28 triangles): 4 x 3 tiles in the plane z = 0
+    (boxes with z0 == z1; tile edges at x = 0 and y = 0.1), a wall in the
+    plane x = 0 and one in the plane y = 0.1.  Both planes hold the default
+    eye (0, 0.1, -1), so box bounds relative to it are exact zeros."""
+    xs = [F(-0.3), F(-0.15), F(0.0), F(0.15), F(0.3)]
+    ys = [F(-0.05), F(0.1), F(0.17), F(0.25)]
+    quads = []
+    for j in range(3):
+        for i in range(4):
+            quads.append([(xs[i], ys[j], 0), (xs[i + 1], ys[j], 0), (xs[i + 1], ys[j + 1], 0), (xs[i], ys[j + 1], 0)])
+    quads.append([(0, 0.0, -0.5), (0, 0.2, -0.5), (0, 0.2, -0.2), (0, 0.0, -0.2)])           # wall in x = 0
+    quads.append([(-0.2, 0.1, -0.6), (0.2, 0.1, -0.6), (0.2, 0.1, -0.3), (-0.2, 0.1, -0.3)])  # wall in y = 0.1
+    v = np.array(quads, F).reshape(-1, 3)
+    f = []
+    for q in range(len(quads)):
+        f += [[4 * q, 4 * q + 1, 4 * q + 2], [4 * q, 4 * q + 2, 4 * q + 3]]
+    return v, np.array(f, np.int32)
+
+
+THRESHOLD_CAM = dict(pos=(0.0, 0.0, -1.0), look_at=(0.0, 0.0, 0.0))  # the centre ray of an odd frame is exactly (0, 0, 1)
+EPS_F_BITS = 0x24E69595  # the smallest float >= 1e-16: 0xE69595 * 2^-77
+
+
+def threshold_triangle(ulps, flip=False, extra=False):
+    """One sliver triangle across the view axis of THRESHOLD_CAM with edges
+    e1 = (a, 0, 0) and e2 = (0, -2^-37, 0), a = (0xE69595 + ulps) * 2^-40, all
+    exact in float32: for the centre ray (0, 0, 1) the determinant is
+    f = +-a * 2^-37 = +-(0xE69595 + ulps) * 2^-77 (the sign by the winding), the
+    smallest float >= 1e-16 at ulps = 0 and the largest one below it at -1.
+    The reference's (double)f < 1e-16 && (double)f > -1e-16 rejects the
+    second and not the first; the ray crosses at u = 1/2, v = 1/4, w = 1.
+    extra: three triangles off to the side, so that the tree has interior
+    nodes (alone, the root is the leaf)."""
+    a = np.array([0x37000000 + 0x669595 + ulps], np.uint32).view(F)[0]
+    b = F(2.0) ** F(-37)
+    v = [(-a / 2, b / 4, 0), (a / 2, b / 4, 0), (-a / 2, -3 * b / 4, 0)]
+    f = [[2, 1, 0] if flip else [1, 2, 0]]  # (read_ply stores a face (A, B, C) as (C, A, B))
+    if extra:
+        v += [(0.2, -0.1, 0.1), (0.3, -0.1, 0.1), (0.25, 0.1, 0.2), (0.2, 0.0, -0.2), (0.3, 0.05, -0.2),
+              (0.25, 0.1, -0.1), (-0.3, -0.1, 0.3), (-0.2, 0.1, 0.3), (-0.25, 0.0, 0.35)]
+        f += [[3, 4, 5], [6, 7, 8], [9, 10, 11]]
+    return np.array(v, F), np.array(f, np.int32)
+
+
+def scaled(verts, cam_kw, e):
+    """The mesh and the camera (pos, look_at, f_w, f_h, focal) times 2^e:
+    exact in float32, so the frame is the same picture at another magnitude."""
+    s = F(2.0) ** F(e)
+    kw = dict(cam_kw)
+    for k in ("f_w", "f_h", "focal"):
+        kw[k] = F(F(kw[k]) * s)
+    for k in ("pos", "look_at"):
+        kw[k] = tuple(float(F(F(x) * s)) for x in kw[k])
+    return (np.asarray(verts, F) * s).astype(F), kw
+
+
+# --------------------------------------------------------------- scene pair
+
+def oracle_nodes(nodes):
+    """A product node array as the oracle's NODE_DTYPE (same field names)."""
+    on = np.zeros(len(nodes), O.NODE_DTYPE)
+    for k in nodes.dtype.names:
+        on[k] = nodes[k]
+    return on
+
+
+class SynthScene:
+    """The same mesh, tree and camera on the product side (Trixel + Camera +
+    Object, created on the first render) and on the oracle side.  Options as
+    helpers.GpuScene: kernel, tile_order, rays, items, coarse, debug, flat."""
+
+    def __init__(self, verts, faces, w, h, cam_kw=None, nodes=None, device=0, **gpu_opts):
+        verts = np.ascontiguousarray(verts, F).reshape(-1, 3)
+        faces = np.ascontiguousarray(faces, np.int32).reshape(-1, 3)
+        self.w, self.h, self.device = w, h, device
+        self.pts, ntri, leafs = R.assemble_mesh(verts, faces)
+        opts, oleafs = O.assemble(verts, np.full(len(faces), 3, np.int32), faces.reshape(-1))
+        assert self.pts.tobytes() == opts.tobytes()
+        if nodes is None:
+            self.nodes = R.kd_build(leafs)
+            self.onodes = O.build_kd(oleafs)
+            for k in self.nodes.dtype.names:  # the product's builder and the literal create_kd restatement
+                assert self.nodes[k].tobytes() == self.onodes[k].astype(self.nodes[k].dtype).tobytes(), k
+        else:
+            self.nodes = np.ascontiguousarray(nodes, self.nodes_dtype())
+            self.onodes = oracle_nodes(self.nodes)
+        self.cam_kw = dict(cam_kw) if cam_kw else None
+        self.okw = {k: v for k, v in (self.cam_kw or {}).items()}
+        self.gpu_opts = gpu_opts
+        self.trixel = self.cam = self.obj = None
+        self._osc = None
+
+    @staticmethod
+    def nodes_dtype():
+        from cpp_cuda_raytracer_dev_amd import _lib
+        return _lib.KD_NODE_DTYPE
+
+    # ---- product
+    def _gpu(self):
+        if self.cam is not None:
+            return
+        from cpp_cuda_raytracer_dev_amd import _lib
+        w, h, device = self.w, self.h, self.device
+        self.trixel = R.Trixel(len(self.pts), self.pts, device=device)
+        self.trixel.set_kd_nodes(self.nodes)
+        if self.cam_kw:
+            kw = default_cam(w, h) | self.cam_kw
+            self.cam = R.Camera(w, h, kw["f_w"], kw["f_h"], kw["focal"], *kw["pos"], *kw["look_at"], *kw["up"],
+                                device=device)
+        else:
+            self.cam = R.Camera.default(w, h, device=device)
+        self.options(**self.gpu_opts)
+        self.obj = R.Object(self.trixel)
+        self.cam.add_object(self.obj)
+
+    def options(self, **opts):
+        """Set camera options by GpuScene's names on the live camera (None: leave)."""
+        from cpp_cuda_raytracer_dev_amd import _lib
+        self._gpu()
+        keys = dict(kernel=_lib.RT_OPT_KERNEL, tile_order=_lib.RT_OPT_TILE_ORDER, rays=_lib.RT_OPT_RAYS,
+                    items=_lib.RT_OPT_ITEMS, coarse=_lib.RT_OPT_COARSE, debug=_lib.RT_OPT_DEBUG, flat=_lib.RT_OPT_FLAT,
+                    pool_cap=_lib.RT_OPT_POOL_CAP)
+        for name, value in opts.items():
+            if value is not None:
+                self.cam.set_option(keys[name], value)
+        return self
+
+    def set_option(self, key, value):
+        self._gpu()
+        self.cam.set_option(key, value)
+
+    def get_option(self, key):
+        self._gpu()
+        return self.cam.get_option(key)
+
+    def render(self, mode=0, xform=None, count=False, shadow=False, aov=False):
+        """-> (argb, hit, counters or None), as helpers.GpuScene.render."""
+        self._gpu()
+        if xform is not None:
+            self.obj.quat.rot_m = np.asarray(xform, F).reshape(3, 4)
+        flags = R.RT_FLAG_WRITE_HIT | (R.RT_FLAG_COUNT if count else 0) | (R.RT_FLAG_SHADOW if shadow else 0) | (
+            R.RT_FLAG_WRITE_AOV if aov else 0)
+        self.obj.render(self.cam, mode=mode, flags=flags)
+        self.cam.color_pixels(R.PHONG_COLOR_TAG)
+        cnt = self.cam.counters() if count else None
+        return self.cam.h_color.copy(), self.cam.h_rmi.copy(), cnt
+
+    # ---- oracle
+    def ocam(self):
+        return O.camera(self.w, self.h, **self.okw)
+
+    def oracle(self, mode=0, xform=None, count=False, shadow=False):
+        """-> (argb, hit, counters), as helpers.oracle_render."""
+        if self._osc is None:
+            self._osc = O.Scene(self.pts, O.default_rad(len(self.pts)), self.onodes, self.ocam())
+        return self._osc.render(mode, xform=xform, nthreads=H.ORACLE_THREADS, shadow=shadow)
+
+    def np_camera(self):
+        kw = default_cam(self.w, self.h) | (self.cam_kw or {})
+        return N.camera(self.w, self.h, f_w=F(kw["f_w"]), f_h=F(kw["f_h"]), focal=F(kw["focal"]), pos=kw["pos"],
+                        la=kw["look_at"], up=kw["up"])
+
+    def oracle_np(self, mode=0, xform=None, shadow=False):
+        """The numpy restatement's (argb, hit, counters[5]) on the same arrays (slow)."""
+        nodes = N.nodes_from_array(self.onodes) if mode == 0 else None
+        argb, hit, cnt = N.render(self.pts, nodes, self.np_camera(), mode=mode, xform=xform, shadow=shadow,
+                                  counters=True)
+        return argb, hit, np.array(cnt, np.uint64)
+
+    def np_planes(self, xform=None):
+        """The ten hit planes [10, h, w] of the KD walk from the numpy
+        restatement, obtained as tests/golden/make_aov.py obtains them."""
+        cam = self.np_camera()
+        S = N.prepare(self.pts, N.nodes_from_array(self.onodes), cam)
+        X = N.IDENT.copy() if xform is None else np.asarray(xform, F)
+        aov = np.zeros((10, self.h, self.w), F)
+        hit = np.zeros((self.h, self.w), np.int64)
+        with np.errstate(all="ignore"):
+            for i in range(self.w * self.h):
+                iy, ix = divmod(i, self.w)
+                rmi, d, out, _ = N.trace_kd(S, X, N.primary_ray(cam, ix, iy))
+                hit[iy, ix] = rmi
+                if rmi >= 0:
+                    aov[:, iy, ix] = [d, *out[0], *out[1], *N.RAD]
+                else:
+                    aov[0, iy, ix] = F(400.0)
+        return aov, hit
+
+    def rays(self):
+        """The oracle's primary rays [h * w, 3] (orc_primary_ray)."""
+        import ctypes as C
+        cam = self.ocam()
+        out = np.zeros((self.w * self.h, 3), F)
+        r = np.zeros(3, F)
+        for i in range(self.w * self.h):
+            iy, ix = divmod(i, self.w)
+            O.lib().orc_primary_ray(C.byref(cam), ix, iy, O._ptr(r))
+            out[i] = r
+        return out
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+    def close(self):
+        for h in (self.cam, self.obj.motion if self.obj is not None else None, self.trixel):
+            if h is not None:
+                h.close()
+        self.cam = self.obj = self.trixel = None
+        if self._osc is not None:
+            self._osc.close()
+            self._osc = None
+
+
+# ------------------------------------------------------------- scene tables
+# Shared by the CPU module (conditions on the oracle) and the GPU module.
+
+W, H_ = 33, 19                                   # the frame of every test unless said otherwise
+SOUP_NS = (1, 2, 3, 4, 5, 8, 9, 33, 257)
+SOUP_SEED = 100                                  # soup(n, SOUP_SEED + n)
+#: two_level_depth per n: no interior root (1), leaf children of the root (2),
+#: one leaf child (3), then floor(log2 n) - 2
+TWO_LEVEL_DEPTH = {1: -1, 2: -1, 3: -1, 4: 0, 5: 0, 8: 1, 9: 1, 33: 3, 257: 6}
+SIGNED_PERM = H.SIGNED_PERM                      # test_gpu_parity._GENERAL_XFS[-1]
+INSIDE_EYE = dict(pos=(0.0, 0.1, -0.05), look_at=(0.0, 0.1, 1.0))   # inside every soup's root box but soup(1)'s
+COPIES = (48, 3, 7)                              # copies(n, k, seed)
+EDGE_NS = (12, 257)
+EDGE_SEED = 300
+GRID_FRAMES = ((33, 19), (7, 5), (1, 1), (32, 18))  # the last has no zero-component ray: the control
+SCALE_N, SCALE_SEED = 16, 6
+SCALE_EXPONENTS = (-8, -20, -21, -22, -23, -24, -25, -26, -40, -50, -53, -56, 7)
+DENORMAL_EXPONENT = -60                          # the primary ray's sum of squares is a denormal float
+TREE_N = 33
+
+
+rot_y = H.rot_y                                  # test_gpu_parity._rot_y
+
+
+PERM_Z = np.array([0, 1, 0, 0, -1, 0, 0, 0, 0, 0, 1, 0], F)  # a quarter turn about the view axis: x <-> y, still facing the grid
+
+#: (name, camera, object transform) of the tiny-tree and edge-triangle tests
+SETTINGS = (("identity", None, None), ("rot", None, rot_y(17.0)), ("xlate", None, rot_y(0.0, (0.01, -0.005, 0.02))),
+            ("inside", INSIDE_EYE, None))
+
+
+def grid_poses(w, h):
+    """(name, camera, object transform) of the grid tests at w x h."""
+    return (("identity", None, None), ("perm", None, SIGNED_PERM), ("perm_z", None, PERM_Z),
+            ("split", grid_eye_on_split(w, h), None))
+
+
+#: the object transforms the hand-made trees render under beside the identity
+TREE_XFS = (("rot", rot_y(17.0)), ("xlate", rot_y(0.0, (0.01, -0.005, 0.02))))
+
+
+def soup_scene(n, w=W, h=H_, cam_kw=None, **opts):
+    return SynthScene(*soup(n, SOUP_SEED + n), w, h, cam_kw=cam_kw, **opts)
+
+
+def scaled_soup(e, w=W, h=H_, **opts):
+    v, f = soup(SCALE_N, SCALE_SEED)
+    v, kw = scaled(v, default_cam(w, h), e)
+    return SynthScene(v, f, w, h, cam_kw=kw, **opts)
+
+
+def grid_eye_on_split(w, h):
+    """A camera whose x and y equal an interior node's s1 of grid()'s tree (a
+    node cut along x and one cut along y, read from the built tree): the
+    camera-relative s1 is an exact zero where rays have zero components."""
+    sc = SynthScene(*grid(), w, h)
+    nodes = sc.nodes
+    pos = [0.0, 0.1, -1.0]
+    for axis in (0, 1):
+        k = np.flatnonzero((nodes["is_leaf"] == 0) & (nodes["cut_flag"] % 3 == axis) &
+                           (nodes["s1"] != F(pos[axis])))  # (the default eye already lies on some: a new place)
+        assert k.size, axis
+        pos[axis] = float(nodes["s1"][k[0]])
+    return dict(pos=tuple(pos), look_at=(pos[0], pos[1], 0.0))
+
+
+SPLIT_FIELD_VARIANTS = ("inflated_split", "shrunk_interior", "shrunk_split")
+
+
+def _shrink(nodes, k, axes):
+    for a in axes:
+        lo, hi = ("x0", "y0", "z0")[a], ("x1", "y1", "z1")[a]
+        mid = F(0.5) * (nodes[lo][k] + nodes[hi][k])
+        nodes[lo][k] = F(0.5) * (nodes[lo][k] + mid)
+        nodes[hi][k] = F(0.5) * (nodes[hi][k] + mid)
+
+
+def tree_variants():
+    """Hand-made trees over soup(33) that rt_scene_set_kd accepts.  ->
+    ((verts, faces), {name: nodes}); "built" is the unmodified tree.
+      swapped   (i) the root's left child with its low and high bound swapped
+                on an axis the root does not cut;
+      inflated  (ii) the root's right child's box 0.25 beyond the root's on
+                every side but its low bound on the root's cut axis;
+      shrunk    (iii) a leaf's box halved on the axes its parent does not cut
+                (the reference's walk never tests a leaf's box: no change).
+    The reference reads a node's split planes from its s1 / s2 fields, which
+    create_kd sets to the left child's high and the right child's low bound on
+    the cut axis.  The variants above keep those two bounds; the variants of
+    SPLIT_FIELD_VARIANTS change them and leave the fields as built:
+      inflated_split   (ii) with that low bound moved out as well;
+      shrunk_interior  an interior node's box halved on x and y;
+      shrunk_split     (iii) on every axis."""
+    v, f = soup(TREE_N, SOUP_SEED + TREE_N)
+    base = SynthScene(v, f, W, H_).nodes
+    out = {"built": base.copy()}
+    root = base[0]
+    L, cut = int(root["left"]), int(root["cut_flag"]) % 3
+    lo_hi = (("x0", "x1"), ("y0", "y1"), ("z0", "z1"))
+    a = base.copy()
+    lo, hi = lo_hi[(cut + 1) % 3]
+    a[lo][L], a[hi][L] = base[hi][L], base[lo][L]
+    out["swapped"] = a
+    for name in ("inflated", "inflated_split"):
+        b = base.copy()
+        for k, d in (("x0", -1), ("x1", 1), ("y0", -1), ("y1", 1), ("z0", -1), ("z1", 1)):
+            if name == "inflated_split" or k != lo_hi[cut][0]:
+                b[k][L + 1] = F(root[k] + F(d) * F(0.25))
+        out[name] = b
+    leaf = int(np.flatnonzero(base["is_leaf"] == 1)[0])
+    pcut = int(base["cut_flag"][int(base["parent"][leaf])]) % 3
+    c = base.copy()
+    _shrink(c, leaf, [k for k in range(3) if k != pcut])
+    out["shrunk"] = c
+    c = base.copy()
+    _shrink(c, leaf, [0, 1, 2])
+    out["shrunk_split"] = c
+    d = base.copy()
+    node = int(base["left"][L])
+    assert base["is_leaf"][node] == 0
+    _shrink(d, node, [0, 1])
+    out["shrunk_interior"] = d
+    for name, nodes in out.items():   # which variants keep s1 / s2 equal to the children's bounds
+        inner = np.flatnonzero(nodes["is_leaf"] == 0)
+        ax = nodes["cut_flag"][inner] % 3
+        s1 = np.choose(ax, [nodes[h][nodes["left"][inner]] for _, h in lo_hi])
+        s2 = np.choose(ax, [nodes[l][nodes["right"][inner]] for l, _ in lo_hi])
+        keeps = bool((s1 == nodes["s1"][inner]).all() and (s2 == nodes["s2"][inner]).all())
+        assert keeps == (name not in SPLIT_FIELD_VARIANTS), name
+    return (v, f), out

@@ -403,10 +403,7 @@ def test_happy_standin_kd_2160p_rows():
     _assert_same((argb[sl], hit[sl]), (oargb[sl], ohit[sl]), "happy 4K band")
 
 
-def _rot_y(deg, t=(0.0, 0.0, 0.0)):
-    a = np.deg2rad(deg)
-    c, s = np.float32(np.cos(a)), np.float32(np.sin(a))
-    return np.array([[c, 0, s, t[0]], [0, 1, 0, t[1]], [-s, 0, c, t[2]]], np.float32).reshape(12)
+_rot_y = H.rot_y  # (shared with tests/synth.py)
 
 
 @pytest.mark.parametrize("xf", [_rot_y(0.0, (0.01, -0.005, 0.02)), _rot_y(17.0), _rot_y(-9.0, (0.0, 0.01, 0.0))])
@@ -733,7 +730,7 @@ def _quat_xform(axis, deg, t):
 # camera's own) exercise root_certain_miss_xf's bounds against the oracle
 _XF_RNG = np.random.default_rng(20261017)
 _GENERAL_XFS = [_quat_xform(_XF_RNG.normal(size=3), _XF_RNG.uniform(-120, 120), _XF_RNG.uniform(-0.03, 0.03, 3))
-                for _ in range(5)] + [np.array([0, 0, 1, 0.01, 0, 1, 0, 0, -1, 0, 0, 0], np.float32)]
+                for _ in range(5)] + [H.SIGNED_PERM]
 
 
 @pytest.mark.parametrize("debug", [None, 4])

@@ -1,0 +1,413 @@
+"""GPU parity on the synthetic edge-case scenes of tests/synth.py: every
+kernel configuration against the oracle, bit-exact on the frame, the hit
+buffer and the visit counters.
+
+The mesh suite (test_gpu_parity.py) renders five natural meshes; these scenes
+reach what no natural mesh does: a root that is a leaf and trees of 2 to 9
+triangles, exact depth ties inside one KD walk, zero ray components meeting
+box bounds of exactly zero (0 * inf = NaN in the slab products), leaf
+arithmetic at the reference's 1e-16 thresholds, trees that raise
+kCamUnordered, and degenerate triangles in the KD leaf test.
+tests/test_synth_cpu.py proves on the oracle alone that each scene has the
+property it is here for, and anchors the oracle's values to the numpy
+restatement.  The frames are 33x19 and each scene keeps one camera whose
+options change in place, so every test takes a fraction of a second.
+"""
+import numpy as np
+import pytest
+
+from cpp_cuda_raytracer_dev_amd import raytracer as R
+from tests import synth as S
+from tests.test_gpu_parity import COARSE, KERNELS, _GENERAL_XFS, _assert_same, _counters_match, _rot_y
+
+pytestmark = pytest.mark.gpu
+
+
+def test_shared_tables():
+    """The transforms of the scene tables are test_gpu_parity's own."""
+    assert len(KERNELS) == 15 and len(COARSE) == 9
+    assert (S.SETTINGS[1][2] == _rot_y(17.0)).all()
+    assert (S.SETTINGS[2][2] == _rot_y(0.0, (0.01, -0.005, 0.02))).all()
+    assert (S.SIGNED_PERM == _GENERAL_XFS[-1]).all()
+
+
+def _kd(sc, want, kernel, xf=None, shadow=False, what=""):
+    """A counted and a timed KD render of sc's live camera equal `want`
+    (the oracle's argb, hit, counters)."""
+    argb, hit, cnt = sc.render(0, xform=xf, count=True, shadow=shadow)
+    _assert_same((argb, hit), want, what + " counted")
+    _counters_match(cnt, want[2], kernel)
+    argb, hit, _ = sc.render(0, xform=xf, shadow=shadow)
+    _assert_same((argb, hit), want, what + " timed")
+
+
+def _flat(sc, want, xf=None, what=""):
+    for variant in (9, 12):
+        sc.options(flat=variant)
+        argb, hit, cnt = sc.render(1, xform=xf, count=True)
+        _assert_same((argb, hit), want, f"{what} flat {variant}")
+        assert [int(cnt[i]) for i in (1, 2, 3)] == [int(want[2][i]) for i in (1, 2, 3)], f"{what} flat {variant}"
+        argb, hit, _ = sc.render(1, xform=xf)
+        _assert_same((argb, hit), want, f"{what} flat {variant} timed")
+
+
+# ---------------------------------------------------------------- tiny trees
+
+@pytest.mark.parametrize("n", S.SOUP_NS)
+def test_tiny_trees(n):
+    """soup(n) for n = 1 (the root is a leaf), 2, 3, 4, 5, 8, 9, 33, 257 under
+    every kernel configuration: at the identity, rotated, translated and with
+    the eye inside the root box; KD counted and timed, the flat list in both
+    forms, and shadow rays on kernel 3."""
+    from cpp_cuda_raytracer_dev_amd import _lib
+    for name, kw, xf in S.SETTINGS:
+        sc = S.soup_scene(n, cam_kw=kw)
+        try:
+            want = sc.oracle(0, xform=xf)
+            want_flat = sc.oracle(1, xform=xf)
+            want_shadow = sc.oracle(0, xform=xf, shadow=True)
+            for kernel, order, rays in KERNELS:
+                what = f"soup {n} {name} k{kernel} o{order} r{rays}"
+                sc.options(kernel=kernel, tile_order=order, rays=rays)
+                _kd(sc, want, kernel, xf, what=what)
+                if n == 1:
+                    assert sc.get_option(_lib.RT_OPT_FAST_USED) == 0, what
+                _flat(sc, want_flat, xf, what=what)
+                if kernel == 3:
+                    _kd(sc, want_shadow, 3, xf, shadow=True, what=what + " shadow")
+            assert sc.trixel.get_option(_lib.RT_SCENE_TWO_LEVEL_DEPTH) == S.TWO_LEVEL_DEPTH[n]
+            if n >= 4:
+                assert S.TWO_LEVEL_DEPTH[n] == int(np.floor(np.log2(n))) - 2
+            assert sc.cam.device_error() == 0, (n, name)
+        finally:
+            sc.close()
+
+
+# ---------------------------------------------- edge triangles in the KD path
+
+@pytest.mark.parametrize("n", S.EDGE_NS)
+def test_edge_triangles_kd(n):
+    """Both windings, zero area, an eye in the triangle's plane, a triangle
+    behind the eye and one across its depth, in the KD leaf test (which
+    recomputes q from d_t - obj_d: hence the transforms), kernels 2 and 3."""
+    sc = S.SynthScene(*S.edge_soup(n, S.EDGE_SEED + n), S.W, S.H_)
+    try:
+        for name, _, xf in S.SETTINGS[:3]:
+            want = {sh: sc.oracle(0, xform=xf, shadow=sh) for sh in (False, True)}
+            for kernel in (2, 3):
+                for rays in (8, 16, 32):
+                    sc.options(kernel=kernel, rays=rays)
+                    for shadow in ((False, True) if kernel == 3 else (False,)):  # shadow rays run in kernel 3
+                        _kd(sc, want[shadow], kernel, xf, shadow=shadow,
+                            what=f"edge soup {n} {name} k{kernel} r{rays} shadow {shadow}")
+        _flat(sc, sc.oracle(1), what=f"edge soup {n}")
+        assert sc.cam.device_error() == 0
+    finally:
+        sc.close()
+
+
+# ----------------------------------------------------------------------- ties
+
+def test_ties_first_visited_wins():
+    """copies(48, 3): every hit pixel has three candidates of the same depth
+    bits; the winner is the copy the reference's DFS visits first (68 pixels
+    where that is not the lowest index, test_synth_cpu.py).  Every kernel
+    configuration, items per lane 1, 2 and 96, a pool of 89, the one-level
+    walk (debug 1024): hit index, colour and counters are the oracle's."""
+    sc = S.SynthScene(*S.copies(*S.COPIES), S.W, S.H_)
+    try:
+        want = sc.oracle(0)
+        want_shadow = sc.oracle(0, shadow=True)
+        _flat(sc, sc.oracle(1), what="copies")
+        for kernel, order, rays in KERNELS:
+            what = f"copies k{kernel} o{order} r{rays}"
+            sc.options(kernel=kernel, tile_order=order, rays=rays, items=2, pool_cap=640, debug=0)  # (the defaults)
+            _kd(sc, want, kernel, what=what)
+            if kernel != 3:
+                continue
+            _kd(sc, want_shadow, 3, shadow=True, what=what + " shadow")
+            for items in (1, 2, 96):
+                sc.options(items=items)
+                _kd(sc, want, 3, what=f"{what} items {items}")
+            sc.options(items=2, pool_cap=89)
+            _kd(sc, want, 3, what=what + " pool 89")
+            sc.options(pool_cap=640, debug=1024)
+            _kd(sc, want, 3, what=what + " one-level walk")
+        assert sc.cam.device_error() == 0
+    finally:
+        sc.close()
+
+
+@pytest.mark.parametrize("rays", [16, 8])
+def test_ties_cost_order(rays):
+    """Tile order 3 after cost feedback: enough frames for the measured order
+    to apply; the tie winners do not depend on the tile order."""
+    import torch
+    sc = S.SynthScene(*S.copies(*S.COPIES), S.W, S.H_, kernel=3, tile_order=3, rays=rays)
+    try:
+        want = sc.oracle(0)
+        sc._gpu()
+        out = torch.zeros(S.W * S.H_, dtype=torch.int32, device="cuda:0")
+        st = torch.cuda.Stream()
+        for _ in range(40):
+            sc.cam.render_into(out, mode=0, stream=st.cuda_stream)
+            st.synchronize()
+        assert (out.cpu().numpy().view(np.uint32) == want[0]).all()
+        _kd(sc, want, 3, what=f"copies cost order r{rays}")
+        assert sc.cam.device_error() == 0
+    finally:
+        sc.close()
+
+
+def test_ties_planes_and_over():
+    """RT_FLAG_WRITE_AOV: the ten planes are the winning copy's (copies share
+    the depth, point, normal and radiance bits, so the planes equal the numpy
+    restatement's and the hit index names the winner).  The scene rendered
+    over itself (rt_render_over) ties at every hit: nothing is written."""
+    import torch
+    w, h, n = S.W, S.H_, S.W * S.H_
+    sc = S.SynthScene(*S.copies(*S.COPIES), w, h)
+    try:
+        planes, nhit = sc.np_planes()
+        want = sc.oracle(0)
+        assert (nhit.reshape(-1) == want[1]).all()
+        for kernel, order, rays in ((2, 0, 0), (3, 2, 32), (3, 3, 16), (3, 3, 8)):
+            sc.options(kernel=kernel, tile_order=order, rays=rays)
+            argb, hit, _ = sc.render(0, aov=True)
+            _assert_same((argb, hit), want, f"copies aov k{kernel} r{rays}")
+            a = sc.cam.aov()
+            got = np.concatenate([a["d"][None], a["pnt"], a["norm"], a["rad"]]).view(np.uint32)
+            bad = np.flatnonzero((got != planes.view(np.uint32)).reshape(10, -1).any(0))
+            assert bad.size == 0, (kernel, rays, bad[:8])
+        dev = torch.device("cuda:0")
+        argb = torch.zeros(n, dtype=torch.int32, device=dev)
+        hit = torch.zeros(n, dtype=torch.int64, device=dev)
+        pl = torch.zeros(10 * n, dtype=torch.float32, device=dev)
+        sc.cam.set_aov(pl, n)
+        for kernel in (2, 3):
+            sc.options(kernel=kernel)
+            sc.cam.render_into(argb, hit, flags=R.RT_FLAG_WRITE_HIT | R.RT_FLAG_WRITE_AOV)
+            torch.cuda.synchronize()
+            d0 = pl[:n].clone()
+            assert (d0.cpu().numpy().view(np.uint32) == planes[0].reshape(-1).view(np.uint32)).all()
+            argb.fill_(0x11111111)
+            hit.fill_(-7)
+            pl[n:].fill_(7.5)
+            sc.cam.render_over(argb, hit)
+            torch.cuda.synchronize()
+            assert (argb == 0x11111111).all() and (hit == -7).all() and (pl[n:] == 7.5).all(), kernel
+            assert torch.equal(pl[:n].view(torch.int32), d0.view(torch.int32)), kernel
+        sc.cam.set_aov(None)
+        assert sc.cam.device_error() == 0
+    finally:
+        sc.close()
+
+
+# ------------------------------------------- zero components and zero bounds
+
+def _grid_case(w, h, name, kw, xf):
+    """grid() at one pose: every kernel and coarse configuration, with and
+    without shadow rays, the double-promoted forms (debug 2048) as well."""
+    from cpp_cuda_raytracer_dev_amd import _lib
+    sc = S.SynthScene(*S.grid(), w, h, cam_kw=kw)
+    try:
+        want = {sh: sc.oracle(0, xform=xf, shadow=sh) for sh in (False, True)}
+        for kernel, order, rays in KERNELS:
+            sc.options(kernel=kernel, tile_order=order, rays=rays, coarse=8, debug=0)
+            what = f"grid {w}x{h} {name} k{kernel} o{order} r{rays}"
+            _kd(sc, want[False], kernel, xf, what=what)
+            if kernel == 3:
+                used = sc.get_option(_lib.RT_OPT_FAST_USED)
+                _kd(sc, want[True], 3, xf, shadow=True, what=what + " shadow")
+                sc.options(debug=2048)
+                _kd(sc, want[False], 3, xf, what=what + " double forms")
+                assert sc.get_option(_lib.RT_OPT_FAST_USED) == 0
+                _kd(sc, want[True], 3, xf, shadow=True, what=what + " shadow, double forms")
+                if name == "identity" and (w, h) != (1, 1):
+                    assert used & 1, f"{what}: the default view proves the float walks"
+        for rays in (32, 16, 8):
+            for coarse, debug in COARSE + [(8, 4 | 2048)]:
+                sc.options(kernel=3, tile_order=2, rays=rays, coarse=coarse, debug=debug or 0)
+                what = f"grid {w}x{h} {name} r{rays} coarse {coarse} debug {debug}"
+                _kd(sc, want[False], 3, xf, what=what)
+                _kd(sc, want[True], 3, xf, shadow=True, what=what + " shadow")
+        assert sc.cam.device_error() == 0
+    finally:
+        sc.close()
+
+
+@pytest.mark.parametrize("pose", range(4), ids=["identity", "perm", "perm_z", "split"])
+@pytest.mark.parametrize("w,h", S.GRID_FRAMES, ids=lambda v: str(v))
+def test_zero_components_and_zero_bounds(w, h, pose):
+    """Axis-aligned quads in planes that hold the eye: rays with a component
+    of exactly zero (odd frames; 32x18 is the control) against box bounds and
+    split planes of exactly zero, where the slab products are 0 * inf = NaN.
+    Signed-permutation transforms carry the zeros to other axes; the "split"
+    eye sits on other split planes of the tree."""
+    name, kw, xf = S.grid_poses(w, h)[pose]
+    _grid_case(w, h, name, kw, xf)
+
+
+# ---------------------------------------------------------------- scale sweep
+
+@pytest.mark.parametrize("e", S.SCALE_EXPONENTS + (S.DENORMAL_EXPONENT,))
+def test_scale_sweep(e):
+    """soup(16) and its camera times 2^e: the same picture while every leaf
+    quantity (f, then the box coordinates) passes the reference's 1e-16
+    thresholds, which the kernels restate as exact float thresholds; at 2^-60
+    the ray's sum of squares is a denormal.  Frame, hit buffer and every
+    visit counter equal the oracle's; where the float walks were used, the
+    double-promoted forms (debug 2048) agree too."""
+    from cpp_cuda_raytracer_dev_amd import _lib
+    sc = S.scaled_soup(e)
+    try:
+        want = sc.oracle(0)
+        for kernel in (2, 3):
+            for rays in (8, 16, 32):
+                sc.options(kernel=kernel, rays=rays, debug=0)
+                what = f"scale 2^{e} k{kernel} r{rays}"
+                _kd(sc, want, kernel, what=what)
+                if kernel == 3 and sc.get_option(_lib.RT_OPT_FAST_USED):
+                    sc.options(debug=2048)
+                    _kd(sc, want, 3, what=what + " double forms")
+                    assert sc.get_option(_lib.RT_OPT_FAST_USED) == 0
+        _flat(sc, sc.oracle(1), what=f"scale 2^{e}")
+        assert sc.cam.device_error() == 0
+    finally:
+        sc.close()
+
+
+@pytest.mark.parametrize("extra", [False, True], ids=["leaf-root", "tree"])
+def test_threshold_triangles(extra):
+    """A sliver whose determinant for the frame's centre ray is exactly the
+    smallest float >= 1e-16 (kept), one ulp below (rejected) and one above,
+    of either sign: the kernels' float form of (double)f < 1e-16 &&
+    (double)f > -1e-16 in the KD leaf test and in the flat list, off by one
+    ulp in either direction, changes the centre pixel."""
+    for flip in (False, True):
+        for ulps in (-1, 0, 1):
+            sc = S.SynthScene(*S.threshold_triangle(ulps, flip, extra), S.W, S.H_, cam_kw=S.THRESHOLD_CAM)
+            try:
+                want = sc.oracle(0)
+                for kernel, order, rays in KERNELS:
+                    sc.options(kernel=kernel, tile_order=order, rays=rays, debug=0)
+                    what = f"threshold {ulps} flip {flip} extra {extra} k{kernel} o{order} r{rays}"
+                    _kd(sc, want, kernel, what=what)
+                    if kernel == 3:
+                        sc.options(debug=2048)
+                        _kd(sc, want, 3, what=what + " double forms")
+                _flat(sc, sc.oracle(1), what=f"threshold {ulps} flip {flip} extra {extra}")
+                assert sc.cam.device_error() == 0
+            finally:
+                sc.close()
+
+
+# ------------------------------------------------------------ hand-made trees
+
+def _tree_case(v, f, name, nodes):
+    from cpp_cuda_raytracer_dev_amd import _lib
+    sc = S.SynthScene(v, f, S.W, S.H_, nodes=nodes)
+    try:
+        want = {sh: sc.oracle(0, shadow=sh) for sh in (False, True)}
+        for kernel, order, rays in KERNELS:
+            sc.options(kernel=kernel, tile_order=order, rays=rays)
+            what = f"tree {name} k{kernel} o{order} r{rays}"
+            _kd(sc, want[False], kernel, what=what)
+            if kernel == 3:
+                used = sc.get_option(_lib.RT_OPT_FAST_USED)
+                if name == "built":
+                    assert used & 1, "the built tree at the default view proves the float walks"
+                if name in ("swapped", "inflated") + S.SPLIT_FIELD_VARIANTS:
+                    assert used == 0, (name, used)
+                _kd(sc, want[True], 3, shadow=True, what=what + " shadow")
+        for xf in (_rot_y(17.0), _rot_y(0.0, (0.01, -0.005, 0.02))):
+            for kernel in (2, 3):
+                sc.options(kernel=kernel, tile_order=2, rays=16)
+                _kd(sc, sc.oracle(0, xform=xf), kernel, xf, what=f"tree {name} k{kernel} moved")
+        assert sc.cam.device_error() == 0
+    finally:
+        sc.close()
+
+
+def test_hand_made_trees():
+    """Trees rt_scene_set_kd accepts but no builder makes: a child box with
+    its low bound above its high bound, a child box larger than its parent's,
+    a leaf box that its triangle sticks out of.  The oracle walks the same
+    nodes; frames and counters are equal.  The first two raise kCamUnordered,
+    so the float walks are refused (the built tree at the same view has them)."""
+    (v, f), trees = S.tree_variants()
+    for name in ("built", "swapped", "inflated", "shrunk"):
+        _tree_case(v, f, name, trees[name])
+
+
+@pytest.mark.parametrize("name", S.SPLIT_FIELD_VARIANTS)
+def test_hand_made_trees_split_fields(name):
+    """Trees whose s1 / s2 fields are not their children's bounds on the cut
+    axis.  The reference (and both oracles) order a node's children by the
+    fields; the kernels read the split planes from the child boxes of the
+    node's record (rec_s1 / rec_s2: the left child's high and the right
+    child's low bound, which create_kd makes equal to the fields).  For a
+    tree where they differ k_cam_nodes raises kCamSplitFields: the walks keep
+    the double forms and take the fields from a side table
+    (TraceParams::split_planes).  Before that the visit counters differed
+    from the oracle's (library vs oracle, interior / leaf visits):
+        inflated_split   kernel 3, shadow render: 11654 vs 11642 interior
+        shrunk_interior  kernel 2, primary rays:  7141 vs 7293 interior
+        shrunk_split     kernel 3, shadow render: 3513 vs 3515 leaf"""
+    (v, f), trees = S.tree_variants()
+    _tree_case(v, f, name, trees[name])
+
+
+# ------------------------------------------ tiny scenes through the frame loop
+
+@pytest.mark.parametrize("n", [1, 2])
+def test_tiny_scenes_frame_loop(n):
+    """A one-triangle scene (leaf root) and a two-triangle one through
+    rt_run_frames with two buffers: frames in flight, and multi-frame
+    launches; every buffer holds the oracle's frame."""
+    import torch
+    from cpp_cuda_raytracer_dev_amd import _lib
+    sc = S.soup_scene(n)
+    try:
+        want = sc.oracle(0)
+        sc._gpu()
+        dev = torch.device("cuda:0")
+        st = torch.cuda.Stream(device=dev)
+        for inflight in (2, _lib.RT_LOOP_MULTIFRAME):
+            bufs = [torch.full((S.W * S.H_,), 0x7BADBEEF, dtype=torch.int32, device=dev) for _ in range(2)]
+            torch.cuda.synchronize()
+            loop = R.FrameLoop(sc.cam, bufs, mode=0, render_stream=st.cuda_stream, event_every=1, inflight=inflight)
+            for frames in (2, 21):
+                _, cnt, _ = loop.run(frames)
+                torch.cuda.synchronize()
+                assert cnt > 0
+                for k, b in enumerate(bufs):
+                    assert (b.cpu().numpy().view(np.uint32) == want[0]).all(), (n, inflight, frames, k)
+            assert sc.cam.device_error(reset=True) == 0
+    finally:
+        sc.close()
+
+
+@pytest.mark.parametrize("nranks", [2, 3])
+def test_grid_band_tiles(nranks):
+    """grid() at 33x9 in band tiles of 2 and 3 ranks, unpacked: the oracle's frame."""
+    import torch
+    w, h = 33, 9
+    sc = S.SynthScene(*S.grid(), w, h)
+    try:
+        want = sc.oracle(0)
+        sc._gpu()
+        npk = R.packed_pixels(w, h, nranks)
+        dev = torch.device("cuda:0")
+        for kernel, order, rays in KERNELS:
+            sc.options(kernel=kernel, tile_order=order, rays=rays)
+            gathered = torch.zeros(nranks * npk, dtype=torch.int32, device=dev)
+            for r in range(nranks):
+                sc.cam.render_into(gathered[r * npk:(r + 1) * npk], mode=0, tile=(nranks, r))
+            frame = torch.zeros(w * h, dtype=torch.int32, device=dev)
+            R.unpack_bands(0, w, h, nranks, gathered, frame)
+            torch.cuda.synchronize()
+            assert (frame.cpu().numpy().view(np.uint32) == want[0]).all(), (nranks, kernel, order, rays)
+        assert sc.cam.device_error() == 0
+    finally:
+        sc.close()
