@@ -401,11 +401,8 @@ __device__ __forceinline__ void slab_fast(f2v bx, f2v by, f2v bz, float ix, floa
 // of lo (r > 0) or of hi (r < 0), known at compile time, and each box takes
 // one max3 and one min3 after its products instead of a min and a max per
 // axis (the same values: with lo <= hi and 1/r of the component's sign, the
-// selected product is the smaller one).  pool_walk_oct instantiates the walk
+// selected product is the smaller one).  trace_unit instantiates the walk
 // per octant, so no per-slot switch is paid.
-#ifndef RT_OCT_WALKS
-#define RT_OCT_WALKS 1
-#endif
 template <int kOct>
 __device__ __forceinline__ void slab_pair_oct(float4 r0, float4 r1, float4 r2, float ix, float iy, float iz,
                                               float& lt0, float& lt1, float& rt0, float& rt1) {
@@ -882,12 +879,6 @@ __device__ __forceinline__ void camera_ray(const TraceParams& P, const Pixel& px
     camera_ray<false>(P, px, live, cam, R, rn);
 }
 
-// Shadow walks on the segment (round 6): 0 follows the whole ray beyond the
-// hit, as rounds 1-5 did (the same images; A/B builds only -- the oracle's
-// counters are the segment walk's).
-#ifndef RT_SHADOW_SEGMENT
-#define RT_SHADOW_SEGMENT 1
-#endif
 // The reference's root visit (TD/Trixel.cu:53,71-95): a leaf root is always
 // visited, an interior root when its slab test passes.  kSeg: a shadow
 // segment's walk, which enters a box only where the segment does (its entry
@@ -904,7 +895,7 @@ __device__ __forceinline__ bool root_pass(const TraceParams& P, const Ray& R, bo
             if (kCount) n_int++;
             has = slab(R, P.root_box[0], P.root_box[1], P.root_box[2], P.root_box[3], P.root_box[4],
                        P.root_box[5], t0, t1);
-            if (kSeg && RT_SHADOW_SEGMENT) has = has && t0 < lim;
+            if (kSeg) has = has && t0 < lim;
             if (kCount && has) n_desc++;
         }
     }
@@ -952,18 +943,16 @@ __device__ __forceinline__ const float4* record_fast(const TraceParams& P, uint3
 // The per-ray data of an item's ray from LDS (see store_ray), as the float4s
 // (q2 = (odz/rz, dir per axis), q3 = (od, ds axis 0), q4 = (ds axes 1-2,
 // Lmax, hit triangle)) the visits read.
-// kFast walks read the first three fields only (direction and 1/r: no
-// offsets, and the direction per cut axis is the component itself).
+// (The fast slots read their fields themselves: ray_fields3, xfast_slot.)
 // kOdP (round 6): a translated nearest-hit walk whose LDS holds six fields
 // only -- the offset od and ds per cut axis (r_a * 1 + r_b * 0 + r_c * 0 of
 // od: od's component, up to the sign of a zero, which no compare sees) are
 // the transform's own, uniform over the wave (xf = P.xf).
-template <bool kTranslated, int kStride, bool kFast = false, bool kOdP = false>
-__device__ __forceinline__ void ray_of(const float2* rd, Ray& Q, float4& q2, float4& q3, float4& q4,
-                                       const float* xf = nullptr) {
+template <bool kTranslated, int kStride, bool kOdP>
+__device__ __forceinline__ void ray_of(const float2* rd, Ray& Q, float4& q2, float4& q3, float4& q4, const float* xf) {
     const float2 z = make_float2(0.0f, 0.0f);
     const float2 f0 = rd[0], f1 = rd[kStride], f2 = rd[2 * kStride];
-    const float2 f3 = kFast ? z : rd[3 * kStride], f4 = kFast ? z : rd[4 * kStride], f5 = kFast ? z : rd[5 * kStride];
+    const float2 f3 = rd[3 * kStride], f4 = rd[4 * kStride], f5 = rd[5 * kStride];
     const float2 f6 = kTranslated ? (kOdP ? make_float2(xf[3], xf[7]) : rd[6 * kStride]) : z;
     const float2 f7 = kTranslated ? (kOdP ? make_float2(xf[11], xf[3]) : rd[7 * kStride]) : z;
     const float2 f8 = kTranslated ? (kOdP ? make_float2(xf[7], xf[11]) : rd[8 * kStride]) : z;
@@ -1014,46 +1003,46 @@ __device__ __forceinline__ void count_order(const Order& o, uint32_t& n_int, uin
     n_desc += ((!first_leaf && o.ka) ? 1u : 0u) + ((o.push_second && !second_leaf && o.kb) ? 1u : 0u);
 }
 
-// The child ordering of an interior node whose own slab values are (t0, t1),
-// from its child-box record's split word r3 and its children's slab values
-// (lt0, lt1) and (rt0, rt1).  kCount: the reference's visit counters of the
-// node's children (when `real`).
-//
-// A value the compiler cannot see through: the double-precision fix-ups of
-// tiny s1 values take it, so they stay behind their (rarely taken) uniform
-// branches instead of being computed for every record and selected.
+// A value the compiler cannot see through: the fast slots' double-precision
+// fix-ups of tiny s1 values take it, so they stay behind their (rarely taken)
+// uniform branches instead of being computed for every record and selected.
 __device__ __forceinline__ float opaque(float x) {
     asm volatile("" : "+v"(x));
     return x;
 }
 
-// kFast (untranslated walks of rays with normal, nonzero components, under
-// the frame proof P.fast): the direction per cut axis is the ray component
-// itself (r_a * 1 + r_b * 0 + r_c * 0 == r_a for finite nonzero r), and the
-// entry test mint1 >= maxt0 - 1e-16 && maxt0 > -1e-16 (TD/Trixel.cu:146) is
-// mint1 >= maxt0: P.fast holds only when every box's maxt0 is >= 2^-20 for
-// every ray of the frame (rt_api.cpp fast_proof), where maxt0 - 1e-16 rounds
-// to a double above the float below maxt0.
+// The child ordering of an interior node whose own slab values are (t0, t1),
+// from its child-box record's split word r3 and its children's slab values
+// (lt0, lt1) and (rt0, rt1).  kCount: the reference's visit counters of the
+// node's children (when `real`).
 // kAny: a shadow segment's walk, which enters a child box only where the
 // segment does: its entry parameter below Lmax (q4.z; root_pass).
-template <bool kTranslated, bool kCount, bool kFast = false, bool kAny = false>
-__device__ __forceinline__ void order_node(const TraceParams& P, const Ray& Q, float4 q2, float4 q3, float4 q4,
-                                           float t0, float t1, float4 r0, float4 r1, float4 r2, float4 r3, float lt0,
-                                           float lt1, float rt0, float rt1, bool real, Order& o, uint32_t& n_int,
-                                           uint32_t& n_desc, uint32_t rec = 0u) {
+// (The fast slots -- fast_slot, xfast_slot, two_level_fast -- carry their own
+// single-precision forms of this ordering.  Under the frame proof P.fast, for
+// rays with normal, nonzero components, the direction per cut axis is the ray
+// component itself (r_a * 1 + r_b * 0 + r_c * 0 == r_a for finite nonzero r),
+// and the entry test mint1 >= maxt0 - 1e-16 && maxt0 > -1e-16
+// (TD/Trixel.cu:146) is mint1 >= maxt0: P.fast holds only when every box's
+// maxt0 is >= 2^-20 for every ray of the frame (rt_api.cpp fast_proof), where
+// maxt0 - 1e-16 rounds to a double above the float below maxt0.)
+template <bool kTranslated, bool kCount, bool kAny>
+__device__ __forceinline__ void order_node(const TraceParams& P, float4 q2, float4 q3, float4 q4, float t0, float t1,
+                                           float4 r0, float4 r1, float4 r2, float4 r3, float lt0, float lt1, float rt0,
+                                           float rt1, bool real, Order& o, uint32_t& n_int, uint32_t& n_desc,
+                                           uint32_t rec) {
     const uint32_t lw = __float_as_uint(r3.z), rw = __float_as_uint(r3.w);
     const uint32_t axis = (lw >> kAxisShift) & 3u;
     const uint32_t L = lw & ~(3u << kAxisShift), Rr = rw & ~kTinyS1Bit;
-    const float dir = kFast ? (axis == 0 ? Q.rx : axis == 1 ? Q.ry : Q.rz) : (axis == 0 ? q2.y : axis == 1 ? q2.z : q2.w);
+    const float dir = axis == 0 ? q2.y : axis == 1 ? q2.z : q2.w;
     const float mx = t0 * dir, mn = t1 * dir;
     // The reference's double-promoted epsilon tests (TD/Trixel.cu:146-157):
     // against s2 through the record's exact float thresholds (k_cam_nodes)
     // unless the object is translated
     // rec: the record's index, for a tree whose split planes are not its
-    // boxes' bounds (TraceParams::split_planes; never under kFast); a lane
-    // whose item is a leaf reads record 0 and drops the result
+    // boxes' bounds (TraceParams::split_planes; never under the proof
+    // P.fast); a lane whose item is a leaf reads record 0 and drops the result
     float s1r = rec_s1(r0, r1, axis), s2r = rec_s2(r1, r2, axis);
-    if (!kFast && P.split_planes) {
+    if (P.split_planes) {
         const float2 pl = P.split_planes[(rec & kLeafBit) ? 0u : rec];
         s1r = pl.x; s2r = pl.y;
     }
@@ -1068,24 +1057,13 @@ __device__ __forceinline__ void order_node(const TraceParams& P, const Ray& Q, f
     } else {
         left_first = mx < r3.y;
         pa = mn > r3.x;
-        if (kFast) {
-            // (float)((double)s1 + 1e-16) == s1 unless s1 is tiny (the
-            // record's flag; the camera's P.tiny_s1 says whether any is):
-            // the double form for those, behind a wave-uniform branch
-            s1 = s1r;
-            if (P.tiny_s1) {
-                const bool tiny = (rw & kTinyS1Bit) != 0;
-                if (__ballot(tiny) != 0ull) s1 = tiny ? pred::add_eps_ref(opaque(s1r)) : s1r;
-            }
-        } else {
-            s1 = pred::add_eps_ref(s1r);
-        }
+        s1 = pred::add_eps_ref(s1r);
     }
     // every term computed, then selected (no exec-mask branches)
     const bool pb = (mn < s1) | (mx < s1);
     const bool push_second = (left_first & pa) | (!left_first & pb);
-    const bool lpass = (kFast ? lt1 >= lt0 : pred::enter_ref(lt0, lt1)) && (!kAny || !RT_SHADOW_SEGMENT || lt0 < q4.z);
-    const bool rpass = (kFast ? rt1 >= rt0 : pred::enter_ref(rt0, rt1)) && (!kAny || !RT_SHADOW_SEGMENT || rt0 < q4.z);
+    const bool lpass = pred::enter_ref(lt0, lt1) && (!kAny || lt0 < q4.z);
+    const bool rpass = pred::enter_ref(rt0, rt1) && (!kAny || rt0 < q4.z);
     const uint32_t first = left_first ? L : Rr;
     const uint32_t second = left_first ? Rr : L;
     const bool first_leaf = (first & kLeafBit) != 0, second_leaf = (second & kLeafBit) != 0;
@@ -1103,21 +1081,15 @@ __device__ __forceinline__ void order_node(const TraceParams& P, const Ray& Q, f
 }
 
 // The slab parameters of an interior record's two child boxes (r0..r2).
-template <bool kFast>
 __device__ __forceinline__ void child_slabs(const Ray& Q, float4 r0, float4 r1, float4 r2, float& lt0, float& lt1,
                                             float& rt0, float& rt1) {
-    if (kFast) {
-        slab_fast(f2v{r0.x, r0.y}, f2v{r0.z, r0.w}, f2v{r1.x, r1.y}, Q.ix, Q.iy, Q.iz, lt0, lt1);
-        slab_fast(f2v{r1.z, r1.w}, f2v{r2.x, r2.y}, f2v{r2.z, r2.w}, Q.ix, Q.iy, Q.iz, rt0, rt1);
-    } else {
-        slab_vals(Q, r0.x, r0.y, r0.z, r0.w, r1.x, r1.y, lt0, lt1);
-        slab_vals(Q, r1.z, r1.w, r2.x, r2.y, r2.z, r2.w, rt0, rt1);
-    }
+    slab_vals(Q, r0.x, r0.y, r0.z, r0.w, r1.x, r1.y, lt0, lt1);
+    slab_vals(Q, r1.z, r1.w, r2.x, r2.y, r2.z, r2.w, rt0, rt1);
 }
 
 // An interior item whose child-box record (r0..r3) has arrived: the node's
 // child ordering (TD/Trixel.cu:146-170) and the children's slab tests.
-template <bool kTranslated, bool kCount, bool kFast = false, bool kAny = false>
+template <bool kTranslated, bool kCount, bool kAny>
 __device__ __forceinline__ void visit_interior(const TraceParams& P, const Ray& Q, float4 q2, float4 q3, float4 q4,
                                                uint4 it, float4 r0, float4 r1, float4 r2, float4 r3, Visit& o,
                                                uint32_t& n_int, uint32_t& n_desc) {
@@ -1125,10 +1097,10 @@ __device__ __forceinline__ void visit_interior(const TraceParams& P, const Ray& 
     const uint32_t marked = it.w & kCodeMarkMask;
     // children's slab parameters from the boxes in this record
     float lt0, lt1, rt0, rt1;
-    child_slabs<kFast>(Q, r0, r1, r2, lt0, lt1, rt0, rt1);
+    child_slabs(Q, r0, r1, r2, lt0, lt1, rt0, rt1);
     Order od;
-    order_node<kTranslated, kCount, kFast, kAny>(P, Q, q2, q3, q4, __uint_as_float(it.y), __uint_as_float(it.z), r0, r1, r2,
-                                           r3, lt0, lt1, rt0, rt1, true, od, n_int, n_desc, it.x);
+    order_node<kTranslated, kCount, kAny>(P, q2, q3, q4, __uint_as_float(it.y), __uint_as_float(it.z), r0, r1, r2, r3, lt0,
+                                          lt1, rt0, rt1, true, od, n_int, n_desc, it.x);
     const uint32_t meta_first = (ray << 26) | (marked << 1);
     const uint32_t meta_second = meta_first | 1u;
     o.ca = make_uint4(od.first, __float_as_uint(od.f0), __float_as_uint(od.f1), meta_first);
@@ -1139,7 +1111,7 @@ __device__ __forceinline__ void visit_interior(const TraceParams& P, const Ray& 
 
 // Visits one item whose record has arrived: a leaf's MT test or an interior
 // node's child ordering and slab tests.
-template <int kStride, bool kTranslated, bool kCount, bool kAny, bool kFast = false, bool kOdP = false>
+template <int kStride, bool kTranslated, bool kCount, bool kAny, bool kOdP>
 __device__ __forceinline__ void visit_item(const TraceParams& P, const float2* rd, uint4 it, float4 r0, float4 r1,
                                            float4 r2, float4 r3, Visit& o, uint32_t& n_int, uint32_t& n_leaf,
                                            uint32_t& n_acc, uint32_t& n_desc) {
@@ -1148,11 +1120,11 @@ __device__ __forceinline__ void visit_item(const TraceParams& P, const float2* r
     // each path reads its own ray fields (read once before the branch, they
     // spilled 3 VGPRs of the 16-ray instance, no faster)
     if (it.x & kLeafBit) {
-        ray_of<kTranslated, kStride, kFast, kOdP>(rd, Q, q2, q3, q4, P.xf);
+        ray_of<kTranslated, kStride, kOdP>(rd, Q, q2, q3, q4, P.xf);
         visit_leaf<kTranslated, kCount, kAny>(Q, q4, it, r0, r1, r2, r3, o, n_leaf, n_acc);
     } else {
-        ray_of<kTranslated, kStride, kFast, kOdP>(rd, Q, q2, q3, q4, P.xf);
-        visit_interior<kTranslated, kCount, kFast, kAny>(P, Q, q2, q3, q4, it, r0, r1, r2, r3, o, n_int, n_desc);
+        ray_of<kTranslated, kStride, kOdP>(rd, Q, q2, q3, q4, P.xf);
+        visit_interior<kTranslated, kCount, kAny>(P, Q, q2, q3, q4, it, r0, r1, r2, r3, o, n_int, n_desc);
     }
 }
 
@@ -1226,12 +1198,9 @@ __device__ __forceinline__ int push_children(uint4* items, int at, const Visit& 
 // one pass over the 64 banks, so each field is its own ds_read_b64 (merged
 // into a ds_read2_b64 the two fields take two passes, counted as bank
 // conflicts: 0.47-0.75 conflict cycles per LDS instruction at C3).
-#ifndef RT_RAY_READ_SPLIT
-#define RT_RAY_READ_SPLIT 1
-#endif
 template <int kStride>
 __device__ __forceinline__ void ray_fields3(const float2* rd, float2& f0, float2& f1, float2& f2) {
-    if (RT_RAY_READ_SPLIT && kStride == RT_RAY_STRIDE32) {
+    if (kStride == RT_RAY_STRIDE32) {
         f0 = rd[0];
         asm volatile("" ::: "memory");
         f1 = rd[kStride];
@@ -1244,7 +1213,7 @@ __device__ __forceinline__ void ray_fields3(const float2* rd, float2& f0, float2
     }
 }
 
-template <int kStride, bool kCount, int kOct = 8>
+template <int kStride, bool kCount, int kOct>
 __device__ __forceinline__ int fast_slot(const TraceParams& P, uint4* items, int at, const float2* s_ray,
                                          unsigned long long* s_key, uint32_t* s_tri, uint4 it, bool act, float4 r0,
                                          float4 r1, float4 r2, float4 r3, uint32_t& n_int, uint32_t& n_leaf,
@@ -1376,7 +1345,7 @@ __device__ __forceinline__ int xfast_slot(const TraceParams& P, uint4* items, in
     slab_pair_xoct<kOct>(r0, r1, r2, ix, iy, iz, f3.x, f3.y, f4.x, lt0, lt1, rt0, rt1);
     // a shadow segment enters a box only below Lmax (root_pass): the exit
     // parameter of a box it does not enter is set below its entry
-    if constexpr (kAny && RT_SHADOW_SEGMENT) {
+    if constexpr (kAny) {
         const float lim = rd[9 * kStride].x;
         lt1 = lt0 < lim ? lt1 : -INFINITY;
         rt1 = rt0 < lim ? rt1 : -INFINITY;
@@ -1433,24 +1402,18 @@ __device__ __forceinline__ int xfast_slot(const TraceParams& P, uint4* items, in
     }
 }
 
-// Record loads by the lanes that use them only (kFast walks of 8- and 16-ray
-// units; RT_MASKED_LOADS32 for 32-ray units).  The walk's busiest unit is the
+// Record loads by the lanes that use them only (nearest-hit kFast walks of
+// every unit but the 32-ray one).  The walk's busiest unit is the
 // vector memory path (r05w: TA busy 0.85, TD busy 0.96 of the knot's cycles),
 // whose cost follows the lanes a load instruction carries, not the distinct
 // addresses: an idle lane that re-reads a live item's record costs as much
 // as a real one, and so does a lane whose buffer load the range check drops
 // (r05y).  Exec-masked loads: knot 1080p +3.9 %, dragon 1080p +11 %; 32-ray
-// units (C3, knot 960x540), whose walks are HBM-bound, lose 3-4 % (r05z).
-// 0: every lane loads (idle lanes a live item's record).
-#ifndef RT_MASKED_LOADS
-#define RT_MASKED_LOADS 1
-#endif
-#ifndef RT_MASKED_LOADS32
-#define RT_MASKED_LOADS32 0
-#endif
+// units (C3, knot 960x540), whose walks are HBM-bound, lose 3-4 % (r05z), so
+// there every lane loads (idle lanes a live item's record).
 template <int kStride>
 constexpr bool masked_loads() {
-    return kStride == RT_RAY_STRIDE32 ? RT_MASKED_LOADS32 != 0 : RT_MASKED_LOADS != 0;
+    return kStride != RT_RAY_STRIDE32;
 }
 
 // Record-load statistics (verdict r05 item 1: "measure live lanes per pop
@@ -1535,8 +1498,9 @@ __device__ __forceinline__ float quad_bcast0(float x) { return __uint_as_float(q
 
 // One two-level iteration over the whole pool (n <= 16 items); returns the
 // new pool size (<= 4n: an item pushes its two children or its four
-// grandchildren).
-template <int kStride, bool kTranslated, bool kCount, bool kAny, int kOrder, bool kFast, bool kOdP = false>
+// grandchildren).  The reference's double forms, for nearest-hit walks (any-hit
+// walks take no two-level iterations, pool_walk).
+template <int kStride, bool kTranslated, bool kCount, bool kOdP>
 __device__ __forceinline__ int two_level_iter(const TraceParams& P, uint4* items, const float2* s_ray,
                                               unsigned long long* s_key, uint32_t* s_tri, int n, int lane,
                                               uint32_t& n_int, uint32_t& n_leaf, uint32_t& n_acc, uint32_t& n_desc) {
@@ -1546,11 +1510,9 @@ __device__ __forceinline__ int two_level_iter(const TraceParams& P, uint4* items
     int l = lane;
     asm volatile("" : "+v"(l));
     const int k = l >> 2, role = l & 3;  // role 0: the item's node; 1 / 2: its left / right child
-    bool act = k < n;
+    const bool act = k < n;
     const uint4 it = items[act ? k : 0];
     __builtin_amdgcn_wave_barrier();
-    if (kAny && (!kCount || kOrder >= 4))
-        if (act && s_key[it.w >> 26] == 0ull) act = false;
     const uint32_t marked = it.w & kCodeMarkMask;
     const bool interior = (it.x & kLeafBit) == 0;
     const int depth = 31 - __builtin_clz(marked);
@@ -1561,17 +1523,17 @@ __device__ __forceinline__ int two_level_iter(const TraceParams& P, uint4* items
     const float4 a0 = pa[0], a1 = pa[1], a2 = pa[2], a3 = pa[3];
     Ray Q;
     float4 q2, q3, q4;
-    ray_of<kTranslated, kStride, kFast, kOdP>(s_ray + (size_t)(it.w >> 26), Q, q2, q3, q4, P.xf);
+    ray_of<kTranslated, kStride, kOdP>(s_ray + (size_t)(it.w >> 26), Q, q2, q3, q4, P.xf);
     // the slab values of the record's two child boxes (role 0: the node's
     // children; roles 1, 2: the child's children), then each lane's node's
     // own values: role 0 the item's, roles 1, 2 what role 0 computed for them
     float at0, at1, bt0, bt1;
-    child_slabs<kFast>(Q, a0, a1, a2, at0, at1, bt0, bt1);
+    child_slabs(Q, a0, a1, a2, at0, at1, bt0, bt1);
     const float xl0 = quad_bcast0(at0), xl1 = quad_bcast0(at1), xr0 = quad_bcast0(bt0), xr1 = quad_bcast0(bt1);
     const float t0 = role == 0 ? __uint_as_float(it.y) : role == 1 ? xl0 : xr0;
     const float t1 = role == 0 ? __uint_as_float(it.z) : role == 1 ? xl1 : xr1;
     Order o;
-    order_node<kTranslated, kCount, kFast, kAny>(P, Q, q2, q3, q4, t0, t1, a0, a1, a2, a3, at0, at1, bt0, bt1, false, o, n_int,
+    order_node<kTranslated, kCount, false>(P, q2, q3, q4, t0, t1, a0, a1, a2, a3, at0, at1, bt0, bt1, false, o, n_int,
                                            n_desc, child ? 2u * it.x + (uint32_t)role : it.x);
     // role 0's verdict on its node's children, to roles 1 and 2
     const uint32_t fl = quad_bcast0((o.left_first ? 1u : 0u) | (o.ka ? 2u : 0u) | (o.kb ? 4u : 0u));
@@ -1597,8 +1559,8 @@ __device__ __forceinline__ int two_level_iter(const TraceParams& P, uint4* items
         Visit v;
         v.ka = v.kb = false; v.cand = false;
         if (role == 0 && act && !interior)
-            visit_leaf<kTranslated, kCount, kAny>(Q, q4, it, a0, a1, a2, a3, v, n_leaf, n_acc);
-        record_candidate<kAny>(s_key, s_tri, it, v);
+            visit_leaf<kTranslated, kCount, false>(Q, q4, it, a0, a1, a2, a3, v, n_leaf, n_acc);
+        record_candidate<false>(s_key, s_tri, it, v);
     }
     return n1 + __builtin_popcountll(m2);
 }
@@ -1766,143 +1728,26 @@ __device__ __forceinline__ int two_level_fast(const TraceParams& P, uint4* items
 // key[ray] = 0; without counters the items of such rays are dropped.
 // Each lane pops up to P.items (1 or 2) items per iteration and fetches their
 // records together, so a lane keeps two memory round trips in flight.
-// Shared record loads (round 6, verdict r05 item 1; RT_SHARED_LOADS).  The
-// vector memory path's cost per wave load is the sum over its 16 lane quads
-// of max(1, distinct 128-B lines its loading lanes touch) cycles
-// (tools/ubench_l1.hip), and a pop's items are runs of the same node for
-// coherent rays: at the knot 1080p a single-slot pop's 42 live lanes touch
-// 8.9 records on average (tools/vmem_stats.py, profiles/r06/vmem/), yet a run
-// that straddles a quad boundary costs that quad a line per run.  So only
-// the first lane of each run (consecutive lanes holding the same ref) loads
-// the record, and the run's other lanes take its 16 dwords from that lane by
-// ds_bpermute (the LDS crossbar, not the vector memory path).  Every lane
-// ends up with the record of its own item, as before.
-// Measured and off (r06e, one box, against RT_SHARED_LOADS 0): the address
-// unit's busy share fell (knot 1080p TA_TA_BUSY 0.77 -> 0.57 per CU cycle)
-// but the data unit stayed busy on 0.92-0.95 of the cycles, stalled on the
-// L1 more (TD_TC_STALL 0.42 -> 0.49), and the 16 ds_bpermute per slot and
-// their waits lengthened every pool iteration: the driver's command 12.44k
-// -> 9.98k FPS (exec-masked run-start loads 10.09k), C4 20.7k -> 17.5k, C3
-// 78.0k -> 66.1k, C5 2,904 -> 2,393.
-#ifndef RT_SHARED_LOADS
-#define RT_SHARED_LOADS 0
-#endif
-// Whether this lane starts a run of equal refs among the active lanes, and
-// the lane of the start of its run (byte address for ds_bpermute).
-__device__ __forceinline__ bool run_start(uint32_t ref, bool act, int lane, int& leader_addr) {
-    const uint32_t key = act ? ref : 0xFFFFFFFFu;  // (no ref is all ones: a leaf's index < 2^31 - 1)
-    // the previous lane's key (DPP wave_shr:1; lane 0 gets the all-ones key)
-    const uint32_t prev = (uint32_t)__builtin_amdgcn_update_dpp((int)0xFFFFFFFF, (int)key, 0x138, 0xF, 0xF, false);
-    const bool start = act && (lane == 0 || prev != key);
-    const unsigned long long S = __ballot(start);
-    const unsigned long long m = S & (~0ull >> (63 - lane));  // starts at or below this lane
-    const int lead = m ? 63 - __builtin_clzll(m) : lane;
-    leader_addr = lead << 2;
-    return start;
-}
-// RT_SHARED_BUF: the run starts' loads as buffer loads whose other lanes
-// read beyond the records (the range check drops them) instead of
-// exec-masked global loads -- no exec-mask branch, so the compiler's wait
-// counts stay exact and slot 1's loads stay in flight while slot 0 is
-// visited (with branches it waits for both groups before slot 0's permutes)
-#ifndef RT_SHARED_BUF
-#define RT_SHARED_BUF 1
-#endif
-typedef unsigned int rt_u32x4 __attribute__((ext_vector_type(4)));
-__device__ __forceinline__ float4 as_f4(rt_u32x4 r) {
-    return make_float4(__uint_as_float(r.x), __uint_as_float(r.y), __uint_as_float(r.z), __uint_as_float(r.w));
-}
-// The record of `ref` (record_fast's offset) through the buffer resource of
-// the camera's records, or zeros without a memory access when !load.
-__device__ __forceinline__ void load_record_buf(__amdgpu_buffer_rsrc_t rsrc, const TraceParams& P, uint32_t ref,
-                                                bool load, float4& r0, float4& r1, float4& r2, float4& r3) {
-    const uint32_t off = load ? (ref << 6) + ((int32_t)ref < 0 ? P.leaf_off : 0u) : 0x80000000u;
-    r0 = as_f4(__builtin_amdgcn_raw_buffer_load_b128(rsrc, (int)off, 0, 0));
-    r1 = as_f4(__builtin_amdgcn_raw_buffer_load_b128(rsrc, (int)(off + 16u), 0, 0));
-    r2 = as_f4(__builtin_amdgcn_raw_buffer_load_b128(rsrc, (int)(off + 32u), 0, 0));
-    r3 = as_f4(__builtin_amdgcn_raw_buffer_load_b128(rsrc, (int)(off + 48u), 0, 0));
-}
-__device__ __forceinline__ float4 share4(float4 v, int addr) {
-    return make_float4(__int_as_float(__builtin_amdgcn_ds_bpermute(addr, __float_as_int(v.x))),
-                       __int_as_float(__builtin_amdgcn_ds_bpermute(addr, __float_as_int(v.y))),
-                       __int_as_float(__builtin_amdgcn_ds_bpermute(addr, __float_as_int(v.z))),
-                       __int_as_float(__builtin_amdgcn_ds_bpermute(addr, __float_as_int(v.w))));
-}
-
-// kX (round 6): the translated kFast slots (xfast_slot) for a translated
-// nearest-hit walk or a shadow walk whose proof holds; its two-level
-// iterations keep the double forms (two_level_iter).
-#ifndef RT_XMASKED_LOADS
-#define RT_XMASKED_LOADS 1
-#endif
-// Quad-transposed record loads (round 6, kFast one-level pops): in load j
-// the four lanes of a quad fetch the four 16-B quarters of quad lane j's
-// 64-B record (lane r the quarter r ^ j), so every quad touches one line per
-// load -- the L1 / texture units' floor of 16 quad-cycles per wave load
-// (profiles/r06/ubench: a load costs the sum over its quads of the distinct
-// lines each touches) -- and a 4 x 4 exchange inside the quad (lane-bit
-// selects and DPP xor reads) returns each lane its own record.
-#ifndef RT_QUAD_LOADS
-#define RT_QUAD_LOADS 0
-#endif
-template <int kCtrl>
-__device__ __forceinline__ float dpp_f(float x) {
-    return __int_as_float(__builtin_amdgcn_mov_dpp(__float_as_int(x), kCtrl, 0xF, 0xF, true));
-}
-template <int kCtrl>
-__device__ __forceinline__ uint32_t dpp_u(uint32_t x) {
-    return (uint32_t)__builtin_amdgcn_mov_dpp((int)x, kCtrl, 0xF, 0xF, true);
-}
-// The byte offset of an item's record from P.inode (record_fast).
-__device__ __forceinline__ uint32_t rec_off(const TraceParams& P, uint32_t ref) {
-    return (ref << 6) + ((int32_t)ref < 0 ? P.leaf_off : 0u);
-}
-// Load j: quad lane r fetches quarter r ^ j of quad lane j's record (every
-// lane of the wave active).
-__device__ __forceinline__ void quad_load(const TraceParams& P, uint32_t off, int lane, float4& x0, float4& x1,
-                                          float4& x2, float4& x3) {
-    const char* base = (const char*)P.inode;
-    const uint32_t q = ((uint32_t)lane & 3u) << 4;
-    const uint32_t o0 = dpp_u<0x00>(off), o1 = dpp_u<0x55>(off), o2 = dpp_u<0xAA>(off), o3 = dpp_u<0xFF>(off);
-    x0 = *(const float4*)(base + o0 + q);
-    x1 = *(const float4*)(base + o1 + (q ^ 0x10u));
-    x2 = *(const float4*)(base + o2 + (q ^ 0x20u));
-    x3 = *(const float4*)(base + o3 + (q ^ 0x30u));
-}
-// One component of the exchange: lane r holds x_j = (quarter r ^ j of lane
-// j's record); y_m = quarter m of lane r's own record = lane (r ^ m)'s
-// x_r, read by a DPP xor-m of t_m, where t_m(s) = x_(s ^ m) (selects by the
-// lane's bits).
-__device__ __forceinline__ void quad_xpose1(float x0, float x1, float x2, float x3, bool b0, bool b1, float& y0,
-                                            float& y1, float& y2, float& y3) {
-    const float p0 = b0 ? x1 : x0, p1 = b0 ? x0 : x1, p2 = b0 ? x3 : x2, p3 = b0 ? x2 : x3;
-    y0 = b1 ? p2 : p0;
-    y1 = dpp_f<0xB1>(b1 ? p3 : p1);  // quad_perm [1,0,3,2]
-    y2 = dpp_f<0x4E>(b1 ? p0 : p2);  // [2,3,0,1]
-    y3 = dpp_f<0x1B>(b1 ? p1 : p3);  // [3,2,1,0]
-}
-__device__ __forceinline__ void quad_xpose(float4& a0, float4& a1, float4& a2, float4& a3, int lane) {
-    const bool b0 = (lane & 1) != 0, b1 = (lane & 2) != 0;
-    float4 y0, y1, y2, y3;
-    quad_xpose1(a0.x, a1.x, a2.x, a3.x, b0, b1, y0.x, y1.x, y2.x, y3.x);
-    quad_xpose1(a0.y, a1.y, a2.y, a3.y, b0, b1, y0.y, y1.y, y2.y, y3.y);
-    quad_xpose1(a0.z, a1.z, a2.z, a3.z, b0, b1, y0.z, y1.z, y2.z, y3.z);
-    quad_xpose1(a0.w, a1.w, a2.w, a3.w, b0, b1, y0.w, y1.w, y2.w, y3.w);
-    a0 = y0; a1 = y1; a2 = y2; a3 = y3;
-}
-#ifndef RT_SHMASKED_LOADS
-#define RT_SHMASKED_LOADS 0
-#endif
-// the translated walks' two-level iterations in the xfast forms (two_level_fast<kXl>)
-#ifndef RT_XTWO_LEVEL
-#define RT_XTWO_LEVEL 1
-#endif
-template <int kCap, int kStride, bool kTranslated, bool kCount, bool kAny, int kOrder = 0, bool kFast = false,
-          int kOct = 8, bool kX = false, bool kOdP = false>
+// kForm: which forms of the reference's tests the walk's visits take.
+//   kWalkRef    the reference's double forms (visit_item, two_level_iter):
+//               any tree, any ray;
+//   kWalkFast   an untranslated nearest-hit walk under the frame proof P.fast
+//               (fast_slot, two_level_fast);
+//   kWalkXFast  (round 6) a translated nearest-hit walk or a shadow walk
+//               whose proof holds (xfast_slot; nearest-hit two-level
+//               iterations two_level_fast<kXl>).
+// The last two are the "kFast walks" of the comments here and in rt_api.cpp.
+enum WalkForm { kWalkRef, kWalkFast, kWalkXFast };
+template <int kCap, int kStride, bool kTranslated, bool kCount, bool kAny, int kOrder = 0, WalkForm kForm = kWalkRef,
+          int kOct = 8, bool kOdP = false>
 __device__ __forceinline__ void pool_walk(const TraceParams& P, uint4* items, const float2* s_ray,
                                           unsigned long long* s_key, uint32_t* s_tri, int n, int lane,
                                           uint32_t& iters, uint32_t& popped, uint32_t& n_int, uint32_t& n_leaf,
                                           uint32_t& n_acc, uint32_t& n_desc) {
+    static_assert(!(kForm == kWalkFast && kAny), "the untranslated fast slots have no any-hit form");
+    static_assert(!(kForm == kWalkFast && kTranslated), "a translated walk's fast slots are kWalkXFast");
+    static_assert(!(kForm == kWalkXFast && !kTranslated), "the translated fast slots read the ray's offset fields");
+    static_assert(!(kOdP && !kTranslated), "kOdP: the offset of a translated walk, from the transform");
     const int cap = min(P.pool_cap, kCap);
     const int slack = P.tree_height + 1;
     // P.items: 1 = one item per lane, 2 = two; 65..128 = two only when the
@@ -1918,14 +1763,14 @@ __device__ __forceinline__ void pool_walk(const TraceParams& P, uint4* items, co
         if (!kAny && n <= RT_TWO_MAX && P.two_depth >= 0 && 4 * n <= cap - slack) {
             iters++;
             popped += (uint32_t)n;
-            if (kFast && !kAny)
+            if (kForm == kWalkFast)
                 n = two_level_fast<kStride, kCount, kOct>(P, items, s_ray, s_key, s_tri, n, lane, n_int, n_leaf, n_acc, n_desc);
-            else if (kX && !kAny && RT_XTWO_LEVEL)
+            else if (kForm == kWalkXFast)
                 n = two_level_fast<kStride, kCount, kOct, true, kOdP>(P, items, s_ray, s_key, s_tri, n, lane, n_int,
                                                                      n_leaf, n_acc, n_desc);
             else
-                n = two_level_iter<kStride, kTranslated, kCount, kAny, kOrder, kFast, kOdP>(P, items, s_ray, s_key, s_tri, n,
-                                                                              lane, n_int, n_leaf, n_acc, n_desc);
+                n = two_level_iter<kStride, kTranslated, kCount, kOdP>(P, items, s_ray, s_key, s_tri, n, lane, n_int,
+                                                                       n_leaf, n_acc, n_desc);
             __builtin_amdgcn_wave_barrier();
             continue;
         }
@@ -1956,46 +1801,19 @@ __device__ __forceinline__ void pool_walk(const TraceParams& P, uint4* items, co
             if (act1 && s_key[it1.w >> 26] == 0ull) act1 = false;
         }
         // both records in flight before either is consumed
-        constexpr bool kFastRec = (kFast && !kAny) || kX;
-        constexpr bool kMasked = (kFast && !kAny && masked_loads<kStride>()) ||
-                                 (kX && (kAny ? RT_SHMASKED_LOADS != 0 : (RT_XMASKED_LOADS != 0 && masked_loads<kStride>())));
+        // (shadow walks load on every lane: exec-masked loads measured mixed)
+        constexpr bool kFastRec = kForm != kWalkRef;
+        constexpr bool kMasked = kFastRec && !kAny && masked_loads<kStride>();
         const float4* p0 = kFastRec ? record_fast(P, it0.x) : record_of(P, it0.x);
         const float4* p1 = kFastRec ? record_fast(P, it1.x) : record_of(P, it1.x);
         float4 a0, a1, a2, a3, b0, b1, b2, b3;
-        constexpr bool kShared = RT_SHARED_LOADS != 0 && kFastRec;
-        constexpr bool kQuad = RT_QUAD_LOADS != 0 && kFast && !kAny && !kX && !kShared;
-        int lead0 = 0, lead1 = 0;
-        bool st0 = false, st1 = false;
-        if (kShared) {
-            st0 = run_start(it0.x, act0, lane, lead0);
-            if (take > 64) st1 = run_start(it1.x, act1, lane, lead1);
-        }
         if (take > 64) {
-            vmem_stat(P, 1, p0, kShared ? st0 : true, act0);
-            vmem_stat(P, 2, p1, kShared ? st1 : true, act1);
+            vmem_stat(P, 1, p0, true, act0);
+            vmem_stat(P, 2, p1, true, act1);
         } else {
-            vmem_stat(P, 0, p0, kShared ? st0 : kMasked ? act0 : true, act0);
+            vmem_stat(P, 0, p0, kMasked ? act0 : true, act0);
         }
-        if (kQuad) {
-            // every lane (idle ones re-read item base's record, a valid one)
-            quad_load(P, rec_off(P, it0.x), lane, a0, a1, a2, a3);
-            if (take > 64) quad_load(P, rec_off(P, it1.x), lane, b0, b1, b2, b3);
-        } else if (kShared && RT_SHARED_BUF) {
-            // the run starts load; the other lanes take their run start's
-            // record (below, by ds_bpermute).  The resource spans the
-            // camera's records (inode, then trec at leaf_off; < 4 GiB)
-            const __amdgpu_buffer_rsrc_t rsrc =
-                __builtin_amdgcn_make_buffer_rsrc((void*)P.inode, (short)0, (int)P.rec_bytes, 0x00020000);
-            load_record_buf(rsrc, P, it0.x, st0, a0, a1, a2, a3);
-            if (take > 64) load_record_buf(rsrc, P, it1.x, st1, b0, b1, b2, b3);
-        } else if (kShared) {
-            if (st0) {
-                a0 = p0[0]; a1 = p0[1]; a2 = p0[2]; a3 = p0[3];
-            }
-            if (take > 64 && st1) {
-                b0 = p1[0]; b1 = p1[1]; b2 = p1[2]; b3 = p1[3];
-            }
-        } else if (kMasked) {
+        if (kMasked) {
             // a pop of more than 64 items fills slot 0: both slots load on
             // every lane, issued together; a smaller pop loads slot 0's live
             // lanes only (an exec-masked second group waits for the first
@@ -2011,31 +1829,20 @@ __device__ __forceinline__ void pool_walk(const TraceParams& P, uint4* items, co
             b0 = p1[0]; b1 = p1[1]; b2 = p1[2]; b3 = p1[3];
         }
         RT_RECORD_FENCE();
-        if (kQuad) quad_xpose(a0, a1, a2, a3, lane);
-        if (kShared) {
-            a0 = share4(a0, lead0); a1 = share4(a1, lead0); a2 = share4(a2, lead0); a3 = share4(a3, lead0);
-        }
         // item 0 is visited, recorded and pushed before item 1 is visited, so
         // its results die before item 1's are made (fewer live VGPRs)
         int total = 0;
-        if (kFast && !kAny) {
+        if (kForm == kWalkFast) {
             total = fast_slot<kStride, kCount, kOct>(P, items, base, s_ray, s_key, s_tri, it0, act0, a0, a1, a2, a3, n_int,
                                                n_leaf, n_acc, n_desc);
             if (take > 64) {
-                if (kQuad) quad_xpose(b0, b1, b2, b3, lane);
-                if (kShared) {
-                    b0 = share4(b0, lead1); b1 = share4(b1, lead1); b2 = share4(b2, lead1); b3 = share4(b3, lead1);
-                }
                 total += fast_slot<kStride, kCount, kOct>(P, items, base + total, s_ray, s_key, s_tri, it1, act1, b0, b1, b2,
                                                     b3, n_int, n_leaf, n_acc, n_desc);
             }
-        } else if (kX) {
+        } else if (kForm == kWalkXFast) {
             total = xfast_slot<kStride, kCount, kAny, (kOrder & 3), kOct, kOdP>(P, items, base, s_ray, s_key, s_tri, it0, act0, a0,
                                                                        a1, a2, a3, n_int, n_leaf, n_acc, n_desc);
             if (take > 64) {
-                if (kShared) {
-                    b0 = share4(b0, lead1); b1 = share4(b1, lead1); b2 = share4(b2, lead1); b3 = share4(b3, lead1);
-                }
                 total += xfast_slot<kStride, kCount, kAny, (kOrder & 3), kOct, kOdP>(P, items, base + total, s_ray, s_key, s_tri,
                                                                             it1, act1, b0, b1, b2, b3, n_int, n_leaf,
                                                                             n_acc, n_desc);
@@ -2045,8 +1852,8 @@ __device__ __forceinline__ void pool_walk(const TraceParams& P, uint4* items, co
             Visit v0;
             v0.ka = v0.kb = false; v0.cand = false;
             if (act0)
-                visit_item<kStride, kTranslated, kCount, kAny, kFast, kOdP>(P, s_ray + (size_t)(it0.w >> 26), it0, a0, a1, a2,
-                                                                      a3, v0, n_int, n_leaf, n_acc, n_desc);
+                visit_item<kStride, kTranslated, kCount, kAny, kOdP>(P, s_ray + (size_t)(it0.w >> 26), it0, a0, a1, a2, a3,
+                                                                     v0, n_int, n_leaf, n_acc, n_desc);
             record_candidate<kAny>(s_key, s_tri, it0, v0);
             total += push_children<kAny, (kOrder & 3)>(items, base + total, v0);
         }
@@ -2057,8 +1864,8 @@ __device__ __forceinline__ void pool_walk(const TraceParams& P, uint4* items, co
             Visit v1;
             v1.ka = v1.kb = false; v1.cand = false;
             if (act1)
-                visit_item<kStride, kTranslated, kCount, kAny, kFast, kOdP>(P, s_ray + (size_t)(it1.w >> 26), it1, b0, b1, b2,
-                                                                      b3, v1, n_int, n_leaf, n_acc, n_desc);
+                visit_item<kStride, kTranslated, kCount, kAny, kOdP>(P, s_ray + (size_t)(it1.w >> 26), it1, b0, b1, b2, b3,
+                                                                     v1, n_int, n_leaf, n_acc, n_desc);
             record_candidate<kAny>(s_key, s_tri, it1, v1);
             total += push_children<kAny, (kOrder & 3)>(items, base + total, v1);
         }
@@ -2072,24 +1879,8 @@ __device__ __forceinline__ void pool_walk(const TraceParams& P, uint4* items, co
     }
 }
 
-// One instance of the shadow walk per octant of its rays (round 6; the
-// primary walk's RT_OCT_WALKS): the slab_pair_xoct near / far selects are
-// compile-time.  C5 3,783 -> 3,838 FPS, knot + shadows 6,276 -> 6,369,
-// dragon + shadows 9,092 -> 9,203 (r06r, interleaved).
-#ifndef RT_SH_OCT
-#define RT_SH_OCT 1
-#endif
-// The root's visit folded into the seeding of kFast walks (trace_unit).
-#ifndef RT_ROOT_VISIT
-#define RT_ROOT_VISIT 1
-#endif
-// ... and of translated primary walks: off, measured 1.4-1.7 % slower on the
-// moving scenes (r06h; primary +1.5-1.9 %, shadow +0.8-1.0 %), cause not
-// isolated
-#ifndef RT_XROOT_VISIT
-#define RT_XROOT_VISIT 0
-#endif
-// The root record, the same for every lane, through the constant address
+// The root record (trace_unit visits the root while it seeds the pool of a
+// kFast walk), the same for every lane, through the constant address
 // space (a uniform address there compiles to scalar loads).
 __device__ __forceinline__ void root_record(const TraceParams& P, float4& q0, float4& q1, float4& q2, float4& q3) {
     typedef const __attribute__((address_space(4))) float cfloat;
@@ -2158,7 +1949,7 @@ __device__ __forceinline__ void trace_unit(const TraceParams& P, WaveLds<kRays, 
     uint32_t iters = 0, popped = 0;
 
     int n;
-    bool fast;  // the walk takes the kFast forms (slab_fast, order_node)
+    bool fast;  // the walk takes the fast slots (fast_slot; translated: xfast_slot)
     int oct = 8;  // the octant every live ray of the unit lies in (slab_pair_oct), 8 = mixed
     {
         // the ray goes to LDS for the walk; shading recomputes it afterwards
@@ -2173,7 +1964,7 @@ __device__ __forceinline__ void trace_unit(const TraceParams& P, WaveLds<kRays, 
         // whose margins cover the offsets, rt_api.cpp fast_proof)
         fast = P.fast && __ballot(live && !(fabsf(R0.rx) >= 0x1p-126f && fabsf(R0.ry) >= 0x1p-126f &&
                                             fabsf(R0.rz) >= 0x1p-126f)) == 0ull;
-        if (RT_OCT_WALKS && fast) {  // (the octant of the object-space rays)
+        if (fast) {  // (the octant of the object-space rays)
             const unsigned long long LV = __ballot(live), PX = __ballot(live && R0.rx > 0.0f),
                                      PY = __ballot(live && R0.ry > 0.0f), PZ = __ballot(live && R0.rz > 0.0f);
             if ((PX == 0ull || PX == LV) && (PY == 0ull || PY == LV) && (PZ == 0ull || PZ == LV))
@@ -2185,26 +1976,24 @@ __device__ __forceinline__ void trace_unit(const TraceParams& P, WaveLds<kRays, 
             S_.tri[lane] = kMiss;
             S_.rn[lane] = rn0;
         }
-        if (RT_ROOT_VISIT && (!kTranslated || RT_XROOT_VISIT) && fast && !(P.root_ref & kLeafBit) && !(kCount && (P.debug & 32))) {
+        if (!kTranslated && fast && !(P.root_ref & kLeafBit) && !(kCount && (P.debug & 32))) {
             // The root visit in the seed (round 6): every ray that enters the
             // root box visits the root's record, the same for every lane, so
             // its 64 B arrive through the scalar cache, and the pool starts
             // one level down (each ray's kept children, pushed with their
             // path codes by fast_slot as a popped root item would push them).
             // A chain-bound unit's pool chain shortens by a level; the visit
-            // set and the counters are the reference's.
+            // set and the counters are the reference's.  Translated primary
+            // walks do not take it: measured 1.4-1.7 % slower on the moving
+            // scenes, cause not isolated.
             float t0, t1;
             const bool has = root_pass<kCount>(P, R0, live, t0, t1, C.n_int, C.n_desc);
             __builtin_amdgcn_wave_barrier();  // (the rays' LDS fields are written)
             float4 q0, q1, q2, q3;
             root_record(P, q0, q1, q2, q3);
             const uint4 it = make_uint4(P.root_ref, __float_as_uint(t0), __float_as_uint(t1), ((uint32_t)lane << 26) | 1u);
-            if constexpr (kTranslated)
-                n = xfast_slot<RL::kStride, kCount, false, 0, 8, kOdP>(P, items, 0, S_.ray, S_.key, S_.tri, it, has, q0, q1,
-                                                                     q2, q3, C.n_int, C.n_leaf, C.n_acc, C.n_desc);
-            else
-                n = fast_slot<RL::kStride, kCount, 8>(P, items, 0, S_.ray, S_.key, S_.tri, it, has, q0, q1, q2, q3,
-                                                      C.n_int, C.n_leaf, C.n_acc, C.n_desc);
+            n = fast_slot<RL::kStride, kCount, 8>(P, items, 0, S_.ray, S_.key, S_.tri, it, has, q0, q1, q2, q3, C.n_int,
+                                                  C.n_leaf, C.n_acc, C.n_desc);
             __builtin_amdgcn_wave_barrier();
             // (counted as the pool iteration it replaces: the units' costs,
             // and so the cost order and its split thresholds, stay as before)
@@ -2223,7 +2012,7 @@ __device__ __forceinline__ void trace_unit(const TraceParams& P, WaveLds<kRays, 
         // or -z; x and y change sign across the frame), the mixed one else;
         // untranslated walks take the kFast slots, translated ones xfast_slot
 #define RT_OCT_WALK(o)                                                                                               \
-    pool_walk<kCap, RL::kStride, kTranslated, kCount, false, 0, !kTranslated, o, kTranslated, kOdP>(                   \
+    pool_walk<kCap, RL::kStride, kTranslated, kCount, false, 0, kTranslated ? kWalkXFast : kWalkFast, o, kOdP>(        \
         P, items, S_.ray, S_.key, S_.tri, n, lane, iters, popped, C.n_int, C.n_leaf, C.n_acc, C.n_desc)
         switch (oct) {
         case 0: RT_OCT_WALK(0); break;
@@ -2239,9 +2028,8 @@ __device__ __forceinline__ void trace_unit(const TraceParams& P, WaveLds<kRays, 
 #undef RT_OCT_WALK
     }
     else
-        pool_walk<kCap, RL::kStride, kTranslated, kCount, false, 0, false, 8, false, kOdP>(P, items, S_.ray, S_.key, S_.tri,
-                                                                                       n, lane, iters, popped,
-                                                            C.n_int, C.n_leaf, C.n_acc, C.n_desc);
+        pool_walk<kCap, RL::kStride, kTranslated, kCount, false, 0, kWalkRef, 8, kOdP>(
+            P, items, S_.ray, S_.key, S_.tri, n, lane, iters, popped, C.n_int, C.n_leaf, C.n_acc, C.n_desc);
     float cam[3];
     Ray R;
     {
@@ -2294,7 +2082,7 @@ __device__ __forceinline__ void trace_unit(const TraceParams& P, WaveLds<kRays, 
         const bool sh_ok = fabsf(Sh.rx) >= 0x1p-126f && fabsf(Sh.ry) >= 0x1p-126f && fabsf(Sh.rz) >= 0x1p-126f &&
                            (P.sh_neg ? sk < 0.0f : sk > 0.0f);
         const bool sh_fast = P.fast_sh && __ballot(sh_live && !sh_ok) == 0ull;
-        if (RT_ROOT_VISIT && sh_fast && !(P.root_ref & kLeafBit)) {
+        if (sh_fast && !(P.root_ref & kLeafBit)) {
             // the root visit in the seed, as for the primary walk (every
             // shadow ray starts at the light)
             float t0, t1;
@@ -2311,8 +2099,12 @@ __device__ __forceinline__ void trace_unit(const TraceParams& P, WaveLds<kRays, 
         } else {
             n = seed_root<kCount, true>(P, items, Sh, sh_live, lane, C.n_int, C.n_desc, lmax);
         }
-        int sh_oct = 8;  // the octant every live shadow ray lies in (slab_pair_xoct), 8 = mixed
-        if (RT_SH_OCT && sh_fast) {
+        // one instance of the shadow walk per octant of its rays, as for the
+        // primary walk (round 6: slab_pair_xoct's near / far selects are
+        // compile-time; C5 3,783 -> 3,838 FPS, knot + shadows 6,276 -> 6,369,
+        // dragon + shadows 9,092 -> 9,203, r06r, interleaved)
+        int sh_oct = 8;  // the octant every live shadow ray lies in, 8 = mixed
+        if (sh_fast) {
             const unsigned long long LV = __ballot(sh_live), PX = __ballot(sh_live && Sh.rx > 0.0f),
                                      PY = __ballot(sh_live && Sh.ry > 0.0f), PZ = __ballot(sh_live && Sh.rz > 0.0f);
             if ((PX == 0ull || PX == LV) && (PY == 0ull || PY == LV) && (PZ == 0ull || PZ == LV))
@@ -2320,22 +2112,18 @@ __device__ __forceinline__ void trace_unit(const TraceParams& P, WaveLds<kRays, 
         }
         if (sh_fast) {
 #define RT_SH_WALK(o)                                                                                                \
-    pool_walk<kCap, RL::kStride, true, kCount, true, kShadow - 1, false, o, true>(                                     \
+    pool_walk<kCap, RL::kStride, true, kCount, true, kShadow - 1, kWalkXFast, o>(                                      \
         P, items, S_.ray, S_.key, S_.tri, n, lane, iters, popped, C.n_int, C.n_leaf, C.n_acc, C.n_desc)
-            if (RT_SH_OCT) {
-                switch (sh_oct) {
-                case 0: RT_SH_WALK(0); break;
-                case 1: RT_SH_WALK(1); break;
-                case 2: RT_SH_WALK(2); break;
-                case 3: RT_SH_WALK(3); break;
-                case 4: RT_SH_WALK(4); break;
-                case 5: RT_SH_WALK(5); break;
-                case 6: RT_SH_WALK(6); break;
-                case 7: RT_SH_WALK(7); break;
-                default: RT_SH_WALK(8); break;
-                }
-            } else {
-                RT_SH_WALK(8);
+            switch (sh_oct) {
+            case 0: RT_SH_WALK(0); break;
+            case 1: RT_SH_WALK(1); break;
+            case 2: RT_SH_WALK(2); break;
+            case 3: RT_SH_WALK(3); break;
+            case 4: RT_SH_WALK(4); break;
+            case 5: RT_SH_WALK(5); break;
+            case 6: RT_SH_WALK(6); break;
+            case 7: RT_SH_WALK(7); break;
+            default: RT_SH_WALK(8); break;
             }
 #undef RT_SH_WALK
         } else
@@ -2449,7 +2237,7 @@ __device__ __forceinline__ bool root_certain_miss_xf(const TraceParams& P, int32
     return mint1 < maxt0 - tol || maxt0 < -tol;
 }
 
-// A whole 8x8 group at once (RT_GROUP_MISS): the unnormalised direction
+// A whole 8x8 group at once: the unnormalised direction
 // D = X3 (n_mod + u_mod fx + v_mod fy) is affine in the pixel, so over the
 // group each D_i lies between its values at the four corners; widened by
 // e_i = 1e-5 sum_j |X_ij| (|n_j| + |u_j| fx_max + |v_j| fy_max) it holds
@@ -2503,10 +2291,6 @@ __device__ __forceinline__ bool group_certain_miss(const TraceParams& P, const U
     return L0 > U1 + margin || U1 < -margin || U0 < -margin;
 }
 
-//
-#ifndef RT_GROUP_MISS
-#define RT_GROUP_MISS 1
-#endif
 // Groups at least 2 pixels outside the root box's screen rectangle
 // (P.far_rect, identity transform only) skip even that: the rectangle is the
 // box's exact projection (in double, from the same float basis), a pixel's
@@ -2732,8 +2516,8 @@ __global__ __launch_bounds__(128) void k_coarse_kd3(TraceParams P) {
         const int32_t j = j0 + g;
         if (j < j1 && !(far_ok && fill_far<kWriteHit, kCount>(P, coarse_unit(P, j), lane, C))) pending |= 1u << g;
     }
-    // the whole-group certain-miss test, one group per lane (RT_GROUP_MISS)
-    if (RT_GROUP_MISS && !(P.root_ref & kLeafBit) && !(P.debug & 1)) {
+    // the whole-group certain-miss test, one group per lane (group_certain_miss)
+    if (!(P.root_ref & kLeafBit) && !(P.debug & 1)) {
         const int32_t jg = j0 + lane;
         const bool sure = lane < kCoarseMax && jg < j1 && ((pending >> lane) & 1u) &&
                           group_certain_miss(P, coarse_unit(P, jg));
