@@ -347,9 +347,13 @@ def phong(pnt, nrm, rmd, rad):
 RAD = (F(0.1), F(0.55), F(0.2))
 
 
-def render(points9, nodes, cam, mode=0, xform=None, shadow=False, segment=True, counters=False):
+def render(points9, nodes, cam, mode=0, xform=None, shadow=False, segment=True, counters=False, rad=None):
     """-> (argb, hit); with counters=True also the five visit counters of
-    oracle.c (interior, leaf, accept, hit pixels, descend), counted here."""
+    oracle.c (interior, leaf, accept, hit pixels, descend), counted here.
+    rad: a per-triangle [ntri, 3] radiance (the hit triangle's row shades the
+    pixel); None is the demo's one material RAD."""
+    if rad is not None:
+        rad = np.asarray(rad, F).reshape(-1, 3)
     cnt = [0, 0, 0, 0, 0] if counters else None
     S = prepare(points9, nodes if mode == 0 else None, cam)
     X = IDENT if xform is None else np.asarray(xform, F)
@@ -369,7 +373,7 @@ def render(points9, nodes, cam, mode=0, xform=None, shadow=False, segment=True, 
                 if rmi >= 0:
                     if cnt is not None:
                         cnt[3] += 1
-                    argb[i] = phong(out[0], out[1], rmd, RAD)
+                    argb[i] = phong(out[0], out[1], rmd, RAD if rad is None else rad[rmi])
                     if shadow and trace_shadow(S, rmi, d, ray, segment, cnt):
                         argb[i] = 0
     if counters:

@@ -7,7 +7,10 @@ reach what no natural mesh does: a root that is a leaf and trees of 2 to 9
 triangles, exact depth ties inside one KD walk, zero ray components meeting
 box bounds of exactly zero (0 * inf = NaN in the slab products), leaf
 arithmetic at the reference's 1e-16 thresholds, trees that raise
-kCamUnordered, and degenerate triangles in the KD leaf test.
+kCamUnordered, degenerate triangles in the KD leaf test, a light in every
+octant of the mesh, astride it and in the planes of its walls (the shadow
+walk's nine instances and its per-wave fall-back), and a radiance of its own
+per triangle.
 tests/test_synth_cpu.py proves on the oracle alone that each scene has the
 property it is here for, and anchors the oracle's values to the numpy
 restatement.  The frames are 33x19 and each scene keeps one camera whose
@@ -411,3 +414,262 @@ def test_grid_band_tiles(nranks):
         assert sc.cam.device_error() == 0
     finally:
         sc.close()
+
+
+# ----------------------------------------------- the light's side of the mesh
+
+K3 = [k for k in KERNELS if k[0] == 3]
+
+
+def _shadow_orders(sc, want, xf, what):
+    """Shadow renders of kernel 3 under every push order, counted and timed."""
+    from cpp_cuda_raytracer_dev_amd import _lib
+    for order in range(4):
+        sc.set_option(_lib.RT_OPT_SHADOW_ORDER, order)
+        _kd(sc, want, 3, xf, shadow=True, what=f"{what} push order {order}")
+
+
+@pytest.mark.parametrize("pose", S.LIGHT_POSE_NAMES)
+def test_shadow_octants(pose):
+    """soup(65) from eyes that put the light in each octant of the mesh
+    ("ppp": every shadow ray has three positive components; the suite's other
+    scenes are all "nnn"), astride it on one or two axes (waves of several
+    octants under a proof held on another axis, sh_axis 1 and 2) and inside
+    its box (no proof).  test_synth_cpu.py shows each pose's signs on
+    the oracle.  Kernel 3 in every configuration and ray width, the four push
+    orders, counted and timed, the double forms (debug 2048), at the identity
+    and under an object rotation and translation (which do not move the light
+    in the walk's frame): frame, hit buffer and counters are the oracle's.
+    The float shadow walks (RT_OPT_FAST_USED & 2) run at every pose but
+    "inside"."""
+    from cpp_cuda_raytracer_dev_amd import _lib
+    sc = S.light_scene(pose)
+    try:
+        want = sc.oracle(0)
+        for kernel, order, rays in KERNELS:
+            sc.options(kernel=kernel, tile_order=order, rays=rays)
+            _kd(sc, want, kernel, what=f"light {pose} k{kernel} o{order} r{rays} no shadow")
+        for xname, xf in (("identity", None),) + S.TREE_XFS:
+            want = sc.oracle(0, xform=xf, shadow=True)
+            for kernel, order, rays in K3:
+                what = f"light {pose} {xname} o{order} r{rays}"
+                sc.options(kernel=3, tile_order=order, rays=rays, debug=0)
+                _shadow_orders(sc, want, xf, what)
+                assert bool(sc.get_option(_lib.RT_OPT_FAST_USED) & 2) == (pose != "inside"), what
+                sc.options(debug=2048)
+                _kd(sc, want, 3, xf, shadow=True, what=what + " double forms")
+                assert sc.get_option(_lib.RT_OPT_FAST_USED) == 0, what
+            for rays in (8, 16, 32):
+                sc.options(kernel=3, tile_order=2, rays=rays, debug=0)
+                _shadow_orders(sc, want, xf, f"light {pose} {xname} r{rays}")
+                assert sc.get_option(_lib.RT_OPT_RAYS_USED) == rays
+        assert sc.cam.device_error() == 0
+    finally:
+        sc.close()
+
+
+@pytest.mark.parametrize("w,h", S.LIGHT_PLANE_FRAMES, ids=lambda v: str(v))
+@pytest.mark.parametrize("which", S.LIGHT_PLANES)
+def test_shadow_light_planes(which, w, h):
+    """Walls in planes that hold the light: shadow rays with a component of
+    exactly zero (156 pixels at 33x19, test_synth_cpu.py) against boxes whose
+    two bounds on that axis are the light's coordinate, where the shadow
+    slabs' products and offsets are 0 * inf and -2 / 0.  "z" holds the
+    shadow proof on x, so its waves with a zero lane fall back from the float
+    walk per wave; "xyz" has no proof; "xz" holds it on y, with zero and
+    tiny x components of either sign in one wave.  Signed permutations carry
+    the zeros to other axes.  Every kernel-3 configuration and the coarse
+    table."""
+    from cpp_cuda_raytracer_dev_amd import _lib
+    sc = S.light_planes_scene(which, w, h)
+    try:
+        for xname, xf in S.LIGHT_PLANE_XFS:
+            want = {sh: sc.oracle(0, xform=xf, shadow=sh) for sh in (False, True)}
+            for kernel, order, rays in K3:
+                sc.options(kernel=3, tile_order=order, rays=rays, coarse=8, debug=0)
+                what = f"light planes {which} {w}x{h} {xname} o{order} r{rays}"
+                _kd(sc, want[False], 3, xf, what=what)
+                _kd(sc, want[True], 3, xf, shadow=True, what=what + " shadow")
+                if xname == "identity":
+                    assert bool(sc.get_option(_lib.RT_OPT_FAST_USED) & 2) == (which != "xyz"), what
+                sc.options(debug=2048)
+                _kd(sc, want[True], 3, xf, shadow=True, what=what + " shadow, double forms")
+                assert sc.get_option(_lib.RT_OPT_FAST_USED) == 0
+            for rays in (32, 16, 8):
+                for coarse, debug in COARSE:
+                    sc.options(kernel=3, tile_order=2, rays=rays, coarse=coarse, debug=debug or 0)
+                    what = f"light planes {which} {w}x{h} {xname} r{rays} coarse {coarse} debug {debug}"
+                    _kd(sc, want[True], 3, xf, shadow=True, what=what + " shadow")
+        assert sc.cam.device_error() == 0
+    finally:
+        sc.close()
+
+
+def test_shadow_entry_ties():
+    """light_tie(): the root box's entry parameter of a shadow ray is exactly
+    Lmax at 48 pixels, one side of it at 58 and the other at 299
+    (test_synth_cpu.py).  The walk enters a box where maxt0 < Lmax, strictly:
+    the descents of the counted renders tell, in the float walks' root pass
+    and in the double forms."""
+    sc = S.SynthScene(*S.light_tie(), S.W, S.H_, cam_kw=S.THRESHOLD_CAM)
+    try:
+        want = {sh: sc.oracle(0, shadow=sh) for sh in (False, True)}
+        for kernel, order, rays in K3:
+            sc.options(kernel=3, tile_order=order, rays=rays, debug=0)
+            what = f"light tie o{order} r{rays}"
+            _kd(sc, want[False], 3, what=what)
+            _shadow_orders(sc, want[True], None, what)
+            sc.options(debug=2048)
+            _kd(sc, want[True], 3, shadow=True, what=what + " double forms")
+        assert sc.cam.device_error() == 0
+    finally:
+        sc.close()
+
+
+def test_shadow_light_on_triangle():
+    """A triangle in the plane of the light with the light on its edge, on an
+    edge of the root box: all 222 shadow walks enter the root at parameter 0
+    and reach leaves (test_synth_cpu.py), the 19 of the triangle's own pixels
+    with segments from Lmax = 0.0283, directions from differences of nearly
+    equal floats, z components of zero or a rounding's worth, and their own
+    triangle among the leaves they test.  No proof: the double forms."""
+    from cpp_cuda_raytracer_dev_amd import _lib
+    v, f, kw = S.light_on_triangle()
+    sc = S.SynthScene(v, f, S.W, S.H_, cam_kw=kw)
+    try:
+        want = {sh: sc.oracle(0, shadow=sh) for sh in (False, True)}
+        for kernel, order, rays in K3 + [(3, 2, 8), (3, 2, 16), (3, 2, 32)]:
+            sc.options(kernel=3, tile_order=order, rays=rays)
+            what = f"light on triangle o{order} r{rays}"
+            _kd(sc, want[False], 3, what=what)
+            _shadow_orders(sc, want[True], None, what)
+            assert sc.get_option(_lib.RT_OPT_FAST_USED) & 2 == 0, what
+            if rays:
+                assert sc.get_option(_lib.RT_OPT_RAYS_USED) == rays
+        assert sc.cam.device_error() == 0
+    finally:
+        sc.close()
+
+
+# ------------------------------------------------------ per-triangle radiance
+
+def _rad_planes(sc, hit):
+    """The three radiance planes [3, n] as bits: rad[hit], zeros at misses."""
+    want = np.zeros((3, hit.size), np.uint32)
+    m = hit >= 0
+    want[:, m] = sc.rad.view(np.uint32)[hit[m]].T
+    return want
+
+
+@pytest.mark.parametrize("table", S.MATERIAL_TABLES)
+def test_materials(table):
+    """soup(65) with a radiance of its own per triangle (every other scene of
+    the suite has the demo's one material, with which green is the largest
+    channel of every lit pixel): uniform random rows, and EDGE_RAD's rows at
+    the edges of phong's max, divide and to_u8.  All three shading sites
+    (kernel 2, kernel 3, the flat list's), the radiance planes (the table's
+    bits at the hit triangle's row), the frame loop and band tiles."""
+    import torch
+    from cpp_cuda_raytracer_dev_amd import _lib
+    w, h, n = S.W, S.H_, S.W * S.H_
+    sc = S.material_scene(table)
+    try:
+        want = sc.oracle(0)
+        want_shadow = sc.oracle(0, shadow=True)
+        want_flat = sc.oracle(1)
+        rad_kd, rad_flat = _rad_planes(sc, want[1]), _rad_planes(sc, want_flat[1])
+        for kernel, order, rays in KERNELS:
+            what = f"{table} k{kernel} o{order} r{rays}"
+            sc.options(kernel=kernel, tile_order=order, rays=rays)
+            _kd(sc, want, kernel, what=what)
+            _flat(sc, want_flat, what=what)
+            if kernel == 3:
+                _kd(sc, want_shadow, 3, shadow=True, what=what + " shadow")
+            # RT_FLAG_WRITE_AOV: the radiance planes (a shadowed pixel keeps its hit's)
+            cases = [(0, False, want, rad_kd), (1, False, want_flat, rad_flat)]
+            if kernel == 3:
+                cases.append((0, True, want_shadow, rad_kd))
+            for mode, shadow, wnt, wrad in cases:
+                for flat in ((9, 12) if mode == 1 else (None,)):
+                    sc.options(flat=flat)
+                    argb, hit, _ = sc.render(mode, shadow=shadow, aov=True)
+                    _assert_same((argb, hit), wnt, f"{what} mode {mode} shadow {shadow} aov")
+                    got = sc.cam.aov()["rad"].view(np.uint32).reshape(3, n)
+                    bad = np.flatnonzero((got != wrad).any(0))
+                    assert bad.size == 0, (what, mode, shadow, bad[:8], got[:, bad[:2]], wrad[:, bad[:2]])
+        # the frame loop: two frames in flight, and multi-frame launches
+        dev = torch.device("cuda:0")
+        st = torch.cuda.Stream(device=dev)
+        sc.options(kernel=3, tile_order=3, rays=0)
+        for inflight in (2, _lib.RT_LOOP_MULTIFRAME):
+            bufs = [torch.full((n,), 0x7BADBEEF, dtype=torch.int32, device=dev) for _ in range(2)]
+            torch.cuda.synchronize()
+            loop = R.FrameLoop(sc.cam, bufs, mode=0, render_stream=st.cuda_stream, event_every=1, inflight=inflight)
+            for frames in (2, 21):
+                _, cnt, _ = loop.run(frames)
+                torch.cuda.synchronize()
+                assert cnt > 0
+                for k, b in enumerate(bufs):
+                    assert (b.cpu().numpy().view(np.uint32) == want[0]).all(), (table, inflight, frames, k)
+        assert sc.cam.device_error(reset=True) == 0
+        # band tiles of 3 ranks, unpacked
+        nranks = 3
+        npk = R.packed_pixels(w, h, nranks)
+        for kernel, order, rays in KERNELS:
+            sc.options(kernel=kernel, tile_order=order, rays=rays)
+            gathered = torch.zeros(nranks * npk, dtype=torch.int32, device=dev)
+            for r in range(nranks):
+                sc.cam.render_into(gathered[r * npk:(r + 1) * npk], mode=0, tile=(nranks, r))
+            frame = torch.zeros(n, dtype=torch.int32, device=dev)
+            R.unpack_bands(0, w, h, nranks, gathered, frame)
+            torch.cuda.synchronize()
+            assert (frame.cpu().numpy().view(np.uint32) == want[0]).all(), (table, kernel, order, rays)
+        assert sc.cam.device_error() == 0
+    finally:
+        sc.close()
+
+
+def test_materials_over():
+    """Two soups with different material tables in one frame (Camera.add_layer,
+    rt_render_over): soup(65) with materials() under soup(33) with EDGE_RAD,
+    rotated.  Frame, hit index and all ten planes, the radiance planes among
+    them, are per pixel those of the nearer of the two single-object renders
+    (test_over_cpu.composite of the two oracle frames and the numpy
+    restatement's planes; 58 pixels where the layer wins over a base hit, 36
+    where it loses, 91 where it alone hits)."""
+    from tests.test_over_cpu import composite
+    (nb, tb, xb), (nl, tl, xl) = S.OVER_LAYERS
+    base, layer = S.material_scene(tb, nb), S.material_scene(tl, nl)
+    obj2 = None
+    try:
+        singles = []
+        for sc, xf, hb in ((base, xb, 0), (layer, xl, nb)):
+            argb, hit, _ = sc.oracle(0, xform=xf)
+            planes, nhit = sc.np_planes(xf)
+            assert (nhit.reshape(-1) == hit).all()
+            singles.append((argb, hit, planes.reshape(10, -1), hb))
+        want = composite(singles)
+        base._gpu()
+        layer._gpu()
+        obj2 = R.Object(layer.trixel)
+        assert base.cam.add_layer(obj2) == 0 and obj2.hit_base == nb
+        obj2.quat.rot_m = np.asarray(xl, np.float32).reshape(3, 4)
+        for kernel, rays in ((2, 0), (3, 8), (3, 16), (3, 32)):
+            base.options(kernel=kernel, rays=rays)
+            for _ in range(2):  # a second frame starts from the base's plain render again
+                base.obj.render(base.cam)
+                obj2.render(base.cam)
+                base.cam.color_pixels()
+                own = base.cam.aov()
+                planes = np.concatenate([own["d"][None], own["pnt"], own["norm"], own["rad"]]).view(np.uint32)
+                for name, g, wv in zip(("argb", "hit", "planes"), (base.cam.h_color, base.cam.h_rmi, planes.reshape(10, -1)),
+                                       want):
+                    bad = np.flatnonzero((g != wv).reshape(-1, g.shape[-1]).any(0))
+                    assert bad.size == 0, (kernel, rays, name, bad.size, bad[:8])
+        for cam in [base.cam, *base.cam._layers.values()]:
+            assert cam.device_error() == 0
+    finally:
+        if obj2 is not None and obj2.motion is not None:
+            obj2.motion.close()
+        base.close()
+        layer.close()

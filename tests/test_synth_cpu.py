@@ -301,3 +301,310 @@ def test_threshold_triangles_sit_on_the_threshold():
         e1, e2 = p[1] - p[0], p[2] - p[0]
         dets.add(float(F(F(F(-e2[1]) * e1[0]) + F(e2[0] * e1[1]))) > 0)
     assert dets == {True, False}   # one winding's determinant is +1e-16, the other's -1e-16
+
+
+# ------------------------------------------- the light's side and the materials
+
+LIGHT_XFS = (("identity", None),) + S.TREE_XFS
+
+
+@pytest.mark.parametrize("pose", S.LIGHT_POSE_NAMES)
+def test_anchor_light_poses(pose):
+    """soup(65) from every eye of light_poses(): without shadow rays, and with
+    them at the identity and under the two object transforms the GPU test
+    renders."""
+    with S.light_scene(pose) as sc:
+        _anchor(sc, 0, what=f"light {pose}")
+        for name, xf in LIGHT_XFS:
+            _anchor(sc, 0, xf, shadow=True, what=f"light {pose} {name} shadow")
+
+
+@pytest.mark.parametrize("which", S.LIGHT_PLANES)
+@pytest.mark.parametrize("w,h", S.LIGHT_PLANE_FRAMES)
+def test_anchor_light_planes(w, h, which):
+    with S.light_planes_scene(which, w, h) as sc:
+        for name, xf in S.LIGHT_PLANE_XFS:
+            for shadow in (False, True):
+                _anchor(sc, 0, xf, shadow=shadow, what=f"light planes {which} {w}x{h} {name} shadow {shadow}")
+
+
+def test_anchor_light_tie():
+    with S.SynthScene(*S.light_tie(), S.W, S.H_, cam_kw=S.THRESHOLD_CAM) as sc:
+        for shadow in (False, True):
+            _anchor(sc, 0, shadow=shadow, what=f"light tie shadow {shadow}")
+
+
+def test_anchor_light_on_triangle():
+    v, f, kw = S.light_on_triangle()
+    with S.SynthScene(v, f, S.W, S.H_, cam_kw=kw) as sc:
+        for shadow in (False, True):
+            _anchor(sc, 0, shadow=shadow, what=f"light on triangle shadow {shadow}")
+
+
+@pytest.mark.parametrize("table", S.MATERIAL_TABLES)
+def test_anchor_materials(table):
+    """Per-triangle radiance through both oracles: KD, KD with shadow rays,
+    the flat list, and the two layers of the composite test."""
+    with S.material_scene(table) as sc:
+        _anchor(sc, 0, what=f"{table}")
+        _anchor(sc, 0, shadow=True, what=f"{table} shadow")
+        _anchor(sc, 1, what=f"{table} flat")
+    for n, tname, xf in S.OVER_LAYERS:
+        with S.material_scene(tname, n) as sc:
+            _anchor(sc, 0, xf, what=f"over layer {tname} {n}")
+
+
+def _shadowed(sc, xform=None):
+    """(hit mask, shadowed mask) of the oracle: a shadowed pixel is a hit
+    whose colour the shadow pass zeroes (and that was not zero before)."""
+    a0, hit, _ = sc.oracle(0, xform=xform)
+    a1, _, _ = sc.oracle(0, xform=xform, shadow=True)
+    m = hit >= 0
+    assert (a0[m] != 0).all() and (a1[~m] == a0[~m]).all() and ((a1 == a0) | (a1 == 0)).all()
+    return m, m & (a1 == 0)
+
+
+def test_light_octants_hold_their_sign():
+    """The eight octant eyes: every hit pixel's shadow ray has the signs of o
+    on all three axes, strictly (no component below 0.33 in magnitude).
+    Measured (hit, shadowed pixels of 627) for o = (x, y, z) in the order of
+    LIGHT_OCTANTS: nnn 341, 155; pnn 309, 86; npn 353, 133; ppn 343, 110; nnp
+    351, 117; pnp 321, 91; npp 350, 140; ppp 329, 44."""
+    want = dict(nnn=(341, 155), pnn=(309, 86), npn=(353, 133), ppn=(343, 110), nnp=(351, 117), pnp=(321, 91),
+                npp=(350, 140), ppp=(329, 44))
+    assert len(S.LIGHT_OCTANTS) == 8 == len({tuple(o) for o in S.LIGHT_OCTANTS})
+    for o in S.LIGHT_OCTANTS:
+        name = S._pose_name(o)
+        sc = S.light_scene(name)
+        m, sh = _shadowed(sc)
+        pix, dirs, _ = S.shadow_rays(sc)
+        assert (pix == np.flatnonzero(m)).all()
+        assert (np.sign(dirs) == np.array(o, F)).all(), name
+        assert np.abs(dirs).min() > 0.33
+        assert (int(m.sum()), int(sh.sum())) == want[name], (name, int(m.sum()), int(sh.sum()))
+        assert sh.sum() >= 20 and (m & ~sh).sum() >= 20
+
+
+def _mixed_runs(pix, comp, w, width):
+    """The aligned runs of `width` pixels of one row (x0 a multiple of width)
+    in which hit pixels with comp > 0 and with comp < 0 both occur."""
+    runs = {}
+    for p, c in zip(pix, comp):
+        runs.setdefault((int(p) // w, (int(p) % w) // width), set()).add(bool(c > 0))
+    return [k for k, s in runs.items() if len(s) == 2]
+
+
+def test_light_straddles_mix_signs_inside_a_unit():
+    """The six straddle eyes: on each straddled axis (o = 0) both signs occur,
+    and they occur together inside aligned runs of 8 pixels of one row, which
+    unit_pixel (rt_kernels_impl.h) gives to one wave's unit at 8, 16 and 32
+    rays (8 columns from a multiple of 8, rays / 8 rows), and inside aligned
+    runs of 4, the half rows of a split 8-ray unit (kd3_block): such waves
+    hold rays of several octants.  On the other axes the sign is o's.  No
+    component is zero.  Measured per pose (hit, shadowed; per straddled axis
+    negative / positive pixels, mixed runs of 8, of 4):
+        zpp 349, 108; x 183 / 166, 19, 19
+        pzn 339, 124; y 178 / 161, 23, 19
+        npz 332, 129; z 200 / 132, 15, 13
+        zzp 332,  84; x 180 / 152, 21, 19; y 191 / 141, 11, 9
+        znz 322, 108; x 170 / 152, 25, 22; z 190 / 132, 16, 15
+        pzz 324,  97; y 170 / 154, 23, 23; z 172 / 152, 17, 15"""
+    want = dict(zpp=(349, 108), pzn=(339, 124), npz=(332, 129), zzp=(332, 84), znz=(322, 108), pzz=(324, 97))
+    for o in S.LIGHT_STRADDLES:
+        name = S._pose_name(o)
+        sc = S.light_scene(name)
+        m, sh = _shadowed(sc)
+        pix, dirs, _ = S.shadow_rays(sc)
+        assert (dirs != 0).all()
+        assert (int(m.sum()), int(sh.sum())) == want[name], (name, int(m.sum()), int(sh.sum()))
+        assert sh.sum() >= 20 and (m & ~sh).sum() >= 20
+        for k in range(3):
+            if o[k] != 0:
+                assert (np.sign(dirs[:, k]) == o[k]).all(), (name, k)
+                continue
+            assert (dirs[:, k] < 0).sum() >= 20 and (dirs[:, k] > 0).sum() >= 20, (name, k)
+            assert len(_mixed_runs(pix, dirs[:, k], S.W, 8)) >= 1, (name, k)
+            assert len(_mixed_runs(pix, dirs[:, k], S.W, 4)) >= 1, (name, k)
+        r = sc.nodes[0]   # the light (eye + 2) within the root box's range exactly on the straddled axes
+        light = [F(F(p) + F(2)) for p in sc.cam_kw["pos"]]
+        inside = [bool(r[lo] < light[k] < r[hi]) for k, (lo, hi) in enumerate((("x0", "x1"), ("y0", "y1"), ("z0", "z1")))]
+        assert inside == [c == 0 for c in o], name
+
+
+def test_light_inside_the_root_box():
+    """The "inside" eye: the light lies inside soup(65)'s root box on every
+    axis, off its centre; both signs occur on every axis (x 35 / 291, y 249 /
+    77, z 134 / 192 negative / positive of 326 hit pixels), so no axis can
+    prove the shadow walk.  No pixel is shadowed, at this or at any other
+    light inside the box: every slab's entry parameter of the root is
+    negative there and the reference's walk enters no box that holds its
+    ray's origin (maxt0 > -1e-16, TD/Trixel.cu:146; edge_soup()'s docstring
+    has the same for the eye), so each shadow walk ends at the root, 326
+    interior visits and no descent.  (An inside light that shadows a pixel
+    does not exist for this walk; the straddle eyes are the ones with a light
+    within the box's range on some axes and shadows.)"""
+    sc = S.light_scene("inside")
+    m, sh = _shadowed(sc)
+    pix, dirs, _ = S.shadow_rays(sc)
+    assert int(m.sum()) == 326
+    for k, (neg, pos) in enumerate(((35, 291), (249, 77), (134, 192))):
+        assert (int((dirs[:, k] < 0).sum()), int((dirs[:, k] > 0).sum())) == (neg, pos), k
+    r = sc.nodes[0]
+    light = [F(F(p) + F(2)) for p in sc.cam_kw["pos"]]
+    assert r["x0"] < light[0] < r["x1"] and r["y0"] < light[1] < r["y1"] and r["z0"] < light[2] < r["z1"]
+    assert int(sh.sum()) == 0
+    c0, c1 = sc.oracle(0)[2], sc.oracle(0, shadow=True)[2]
+    assert int(c1[0]) - int(c0[0]) == 326 and int(c1[4]) == int(c0[4]) and int(c1[1]) == int(c0[1])
+
+
+def test_light_planes_zero_components():
+    """light_planes() from THRESHOLD_CAM: hit pixels whose shadow ray has a
+    component of exactly +-0, per axis x / y / z, and how many of those
+    pixels the oracle shadows / leaves lit:
+        "z"    33x19 338 hits,  0 / 0 / 156, 135 / 21    32x18 288,  0 / 0 / 140, 122 / 18
+               7x5    18 hits,  0 / 0 / 6,     5 / 1     1x1 no hit
+        "xyz"  33x19 350 hits, 10 / 0 / 156, 135 / 31    32x18 305, 11 / 0 / 140, 122 / 29
+               7x5    18 hits,  0 / 0 / 6,     5 / 1     1x1 no hit
+        "xz"   33x19 359 hits, 16 / 0 / 156, 135 / 37    32x18 316, 16 / 0 / 140, 122 / 34
+               7x5    18 hits,  0 / 0 / 6,     5 / 1     1x1 no hit
+    (32x18 is no control here: a third data point.  The wall in y = 2 lies
+    above the frame; it is there so that no axis proves the shadow walk.)
+    The walls' boxes have equal bounds on their plane's axis, the light's
+    coordinate: relative to the light exact zeros."""
+    want = {("z", 33, 19): (338, (0, 0, 156), 135, 21), ("z", 32, 18): (288, (0, 0, 140), 122, 18),
+            ("z", 7, 5): (18, (0, 0, 6), 5, 1), ("z", 1, 1): (0, (0, 0, 0), 0, 0),
+            ("xyz", 33, 19): (350, (10, 0, 156), 135, 31), ("xyz", 32, 18): (305, (11, 0, 140), 122, 29),
+            ("xyz", 7, 5): (18, (0, 0, 6), 5, 1), ("xyz", 1, 1): (0, (0, 0, 0), 0, 0),
+            ("xz", 33, 19): (359, (16, 0, 156), 135, 37), ("xz", 32, 18): (316, (16, 0, 140), 122, 34),
+            ("xz", 7, 5): (18, (0, 0, 6), 5, 1), ("xz", 1, 1): (0, (0, 0, 0), 0, 0)}
+    for which in S.LIGHT_PLANES:
+        v, f = S.light_planes(which)
+        assert len(f) == {"z": 25, "xz": 27, "xyz": 29}[which] <= 257
+        for w, h in S.LIGHT_PLANE_FRAMES:
+            sc = S.light_planes_scene(which, w, h)
+            m, sh = _shadowed(sc)
+            pix, dirs, _ = S.shadow_rays(sc)
+            zero = dirs == 0
+            anyz = zero.any(axis=1)
+            got = (int(m.sum()), tuple(int(x) for x in zero.sum(axis=0)), int((anyz & sh[pix]).sum()),
+                   int((anyz & ~sh[pix]).sum()))
+            assert got == want[which, w, h], (which, w, h, got)
+            if (w, h) == (33, 19):
+                assert anyz.sum() >= 100 and got[2] >= 20 and got[3] >= 20
+                if which != "z":
+                    assert (zero.sum(axis=0) > 0).sum() >= 2
+            r = sc.nodes[0]
+            assert (r["x1"] < 2) == (which == "z") and r["z0"] < 1 < r["z1"]
+            assert (r["y1"] < 2) == (which != "xyz")         # "xz": x fails, the proof holds on y
+            if which == "xyz":
+                assert r["x0"] < 2 <= r["x1"] and r["y0"] < 2 <= r["y1"]
+        leaf = sc.nodes[sc.nodes["is_leaf"] == 1]
+        assert ((leaf["z0"] == 1) & (leaf["z1"] == 1)).sum() == 24
+        if "x" in which:
+            assert ((leaf["x0"] == 2) & (leaf["x1"] == 2)).sum() == 2
+        if which == "xyz":
+            assert ((leaf["y0"] == 2) & (leaf["y1"] == 2)).sum() == 2
+
+
+def test_light_on_triangle_walks_short_segments():
+    """light_on_triangle(): the replaced triangle lies in the plane z = the
+    light's z with the light at the midpoint of its edge in x = the light's
+    x; both coordinates are the root box's x0 and z0 bit for bit, and every
+    other triangle lies beyond them.  Measured at 33x19: 222 hit pixels, 19 of
+    them the triangle's, which are the 19 smallest Lmax of the frame (0.0283
+    to 0.135; the largest is 1.132).  Every one of the 222 shadow walks enters
+    the root and visits a leaf (the 19 in-plane ones one to three leaves each,
+    their own triangle's among them); 13 pixels are shadowed, 209 lit, none
+    of the triangle's own (no triangle lies in its plane between it and the
+    light)."""
+    v, f, kw = S.light_on_triangle()
+    light = np.array([F(F(p) + F(2)) for p in kw["pos"]], F)
+    t = v[f[S.LIGHT_TRI]]
+    assert (t[:, 2] == light[2]).all() and (t[:2, 0] == light[0]).all() and t[2, 0] > light[0]
+    assert t[0, 1] < light[1] < t[1, 1]                       # the light on the edge t0-t1
+    others = np.delete(v.reshape(-1, 3, 3), S.LIGHT_TRI, axis=0)
+    assert (others[..., 0] > light[0]).all() and (others[..., 2] > light[2]).all()
+    sc = S.SynthScene(v, f, S.W, S.H_, cam_kw=kw)
+    r = sc.nodes[0]
+    assert r["x0"] == light[0] and r["z0"] == light[2] and r["y0"] < light[1] < r["y1"]
+    m, sh = _shadowed(sc)
+    _, hit, _ = sc.oracle(0)
+    pix, _, lmax = S.shadow_rays(sc)
+    vpix, occ, desc, leaf = S.shadow_visits(sc)
+    assert (vpix == pix).all() and (occ == sh[pix]).all()
+    mine = hit[pix] == S.LIGHT_TRI
+    assert (int(m.sum()), int(mine.sum()), int(sh.sum())) == (222, 19, 13)
+    assert lmax[mine].max() < lmax[~mine].min() and lmax.min() == lmax[mine].min()
+    assert (desc > 0).all() and (leaf > 0).all()              # every shadow walk descends to leaves
+    assert set(leaf[mine].tolist()) == {1, 2, 3} and not occ[mine].any()
+    assert sh.sum() >= 1 and (m & ~sh).sum() >= 1
+    c0, c1 = sc.oracle(0)[2], sc.oracle(0, shadow=True)[2]
+    assert int(c1[4]) - int(c0[4]) == int(desc.sum()) and int(c1[1]) - int(c0[1]) == int(leaf.sum())
+    assert (round(float(lmax.min()), 4), round(float(lmax[mine].max()), 3)) == (0.0283, 0.135)
+    assert lmax.min() == F(0.028286124) and 1.13 < lmax.max() < 1.14
+
+
+def test_materials_vary_the_frame():
+    """soup(65) at the default view, 331 hit pixels.  materials(65): no two
+    triangles share a channel value; the frame differs from the one-material
+    frame at all 331 hit pixels, and at 247 of them the largest channel is not
+    green.  EDGE_RAD cycled: every one of its 11 rows is the material of some
+    hit pixel; the frame's hit pixels hold 395 channel bytes of 0, 460 of 255
+    and 138 strictly between (the all-negative row and the infinities take
+    to_u8's >= 256 branch, NaN and negative ratios its first), and at 262 hit
+    pixels the largest byte is not green's alone."""
+    base = S.soup_scene(S.LIGHT_N)
+    b, bhit, _ = base.oracle(0)
+    m = bhit >= 0
+    assert int(m.sum()) == 331
+    g = (b[m] >> 8) & 255
+    assert (g == 255).all()                      # the one material: green is 255 at every lit pixel
+    got = {}
+    for table in S.MATERIAL_TABLES:
+        sc = S.material_scene(table)
+        a, hit, _ = sc.oracle(0)
+        assert (hit == bhit).all() and (a >> 24 == 0).all() and (a[~m] == b[~m]).all()
+        by = np.stack([(a >> 16) & 255, (a >> 8) & 255, a & 255], 1)[m]
+        got[table] = (int((a != b)[m].sum()), int((by == 0).sum()), int((by == 255).sum()),
+                      int(((by > 0) & (by < 255)).sum()), int((by.argmax(1) != 1).sum()))
+        if table == "edge":
+            assert set((hit[m] % len(S.EDGE_RAD)).tolist()) == set(range(len(S.EDGE_RAD)))
+            assert (sc.rad.view(np.uint32) == S.EDGE_RAD.view(np.uint32)[np.arange(S.LIGHT_N) % 11]).all()
+    assert got["materials"][0] >= m.sum() // 2 and got["materials"][4] >= 1
+    assert got["edge"][1] >= 1 and got["edge"][2] >= 1 and got["edge"][3] >= 1 and got["edge"][4] >= 1
+    assert got == {"materials": (331, 0, 331, 662, 247), "edge": (331, 395, 460, 138, 262)}, got
+
+
+def test_over_layers_interleave():
+    """The two layers of test_materials_over (soup(65) with materials, soup(33)
+    with EDGE_RAD, rotated): pixels where only the base, only the layer, both
+    with the layer nearer, both with the base nearer hit, exact ties, neither:
+    237, 91, 58, 36, 0, 205 of 627."""
+    from tests.test_over_cpu import hit_classes
+    frames = []
+    for n, tname, xf in S.OVER_LAYERS:
+        sc = S.material_scene(tname, n)
+        planes, hit = sc.np_planes(xf)
+        assert (hit.reshape(-1) == sc.oracle(0, xform=xf)[1]).all()
+        frames.append((hit, planes[0]))
+    cls = hit_classes(frames[0][0], frames[0][1], frames[1][0], frames[1][1])
+    assert cls[0] >= 20 and cls[1] >= 5 and cls[2] >= 20 and cls[3] >= 20 and cls[4] == 0, cls
+    assert cls == S.OVER_CLASSES, cls
+
+
+def test_light_tie_entry_equals_lmax():
+    """light_tie() at 33x19: 405 hit pixels, all on the wall.  The root box's
+    entry parameter for the shadow ray equals Lmax bit for bit at 48 of them,
+    is below it at 58 (the walk enters the root) and above it at 299 (it does
+    not): the oracle's descents of the shadow pass are the 58, so entering at
+    maxt0 <= Lmax instead of maxt0 < Lmax would count 106."""
+    sc = S.SynthScene(*S.light_tie(), S.W, S.H_, cam_kw=S.THRESHOLD_CAM)
+    m, sh = _shadowed(sc)
+    pix, dirs, lmax = S.shadow_rays(sc)
+    t0 = S.root_entry(sc, dirs)
+    got = (int(m.sum()), int((t0 == lmax).sum()), int((t0 < lmax).sum()), int((t0 > lmax).sum()))
+    assert got[1] >= 20 and got[2] >= 20 and got[3] >= 20, got
+    c0, c1 = sc.oracle(0)[2], sc.oracle(0, shadow=True)[2]
+    assert int(c1[0]) - int(c0[0]) >= got[0]                 # every shadow ray visits the root
+    assert int(c1[4]) - int(c0[4]) == got[2], (got, c0, c1)  # and descends only where maxt0 < Lmax
+    assert got == (405, 48, 58, 299), got
