@@ -285,6 +285,11 @@ int prepare_camera_object(rt_camera* c) {
     if (!s) return fail(RT_ERR_STATE, "camera has no object (rt_camera_add_object)");
     if (c->prepared_version == s->tree_version + 1) return RT_OK;
     int rc;
+    // The records are rewritten in place (on the null stream) whenever they
+    // fit the buffers the camera has: frames of the previous object or tree
+    // still in flight on the caller's streams would walk them half written
+    // (a smaller scene after a larger one; hipFree waits only when they grow)
+    if ((rc = hip_check(hipDeviceSynchronize(), "camera object prep: frames in flight"))) return rc;
     const int64_t nint4 = std::max<int64_t>(s->d_nodes ? s->ninterior : 0, 1) * 4, ntri4 = (int64_t)s->ntri * 4;
     if (c->rec_cap < nint4 + ntri4) {
         dev_free(c->d_rec);
@@ -2490,6 +2495,17 @@ extern "C" int rt_camera_set_option(rt_camera* c, int32_t key, int32_t value) {
         c->pool_cap = value;
         return RT_OK;
     case kOptDebug:
+        // the record-load statistics accumulate until the option is set again:
+        // they share d_dbg with the per-wave stamps (bit 2), whose records an
+        // earlier render may have left there, and start from zero here (a buffer
+        // of fewer than 32 words is replaced, zeroed, by the next render)
+        if ((value & 16384) && c->d_dbg && c->dbg_cap >= 32) {
+            DeviceGuard g(c->device);
+            int rc;
+            if ((rc = hip_check(hipDeviceSynchronize(), "debug option sync")) ||
+                (rc = hip_check(hipMemset(c->d_dbg, 0, sizeof(uint64_t) * 32), "memset vstat")))
+                return rc;
+        }
         c->debug = value;
         return RT_OK;
     case kOptShadowOrder:

@@ -2301,7 +2301,10 @@ __device__ __forceinline__ bool group_certain_miss(const TraceParams& P, const U
 // which each pixel checks.
 __device__ __forceinline__ bool far_group(const TraceParams& P, const Unit& G) {
     const int32_t y0 = (P.rank + G.slot * P.nranks) * kTileH;
-    return G.x0 + 7 < P.far_rect[0] || G.x0 > P.far_rect[1] || y0 + 7 < P.far_rect[2] || y0 > P.far_rect[3];
+    // (y0 >= P.h: a slot past the frame's last band, which a rank of several
+    // has when the bands do not divide evenly; it holds no pixel, and a box
+    // whose rectangle reaches the frame's top edge would otherwise claim it)
+    return y0 >= P.h || G.x0 + 7 < P.far_rect[0] || G.x0 > P.far_rect[1] || y0 + 7 < P.far_rect[2] || y0 > P.far_rect[3];
 }
 
 __device__ __forceinline__ bool ray_has_tiny_component(const TraceParams& P, int32_t ix, int32_t iy) {
