@@ -14,31 +14,11 @@
 #include <string>
 #include <vector>
 
+#include "rt_hip.h"
 #include "rt_internal.h"
+#include "tile_order.h"
 
 using namespace rt;
-
-// A tile grid's cost-order key (ensure_order): tile shape, grid size, ranks,
-// fine-region origin, rays per wave.
-constexpr int kOrderKey = 9;
-
-// A moving object's screen rectangle changes every frame, so its fine grid
-// did too: every frame got a new tile order slot, and the cost order (tile
-// order 3) never applied (its samples were always of a stale grid).  Renders
-// of a transformed object (an identity transform keeps its exact region:
-// nothing moves, and the margin would turn fused far groups into fine tiles)
-// keep the fine region the camera last chose while the exact one stays
-// inside it and covers at least half of it; a new region is chosen with a
-// margin of 1/8 of its size (at least 2 tile columns and 1 band slot) on
-// every side.  Any region that contains the exact one renders the same frame
-// (a fine tile runs the exact root test; the far groups outside it are the
-// same proof, set_fine_region).  rt_frame_rect derives the gather rectangle
-// without it (every rank alone, no state).  Debug bit 256: off.
-struct Hold {
-    bool valid = false;
-    int32_t key[6] = {0, 0, 0, 0, 0, 0};  // tile_w, tile_h, nranks, rank, groups_x, nslots
-    int32_t tx0 = 0, tx1 = -1, s0 = 0, s1 = -1;
-};
 
 struct rt_scene {
     int device = 0;
@@ -98,7 +78,10 @@ struct rt_camera {
     float4* d_rec = nullptr;
     int64_t rec_cap = 0;             // in float4
     uint32_t leaf_off = 0;
-    int kernel_version = 3;          // kOptKernel
+    // kOptKernel: the KD kernel a render runs.  Every kernel handles any tree
+    // the LDS stack admits (height <= kMaxDepth; rt_scene_set_kd rejects
+    // taller ones): kernel 3's marked path codes take height + 1 <= 25 bits.
+    int kernel_version = 3;
     int tile_order = 3;              // kOptTileOrder
     // kOptDebug (diagnostics): 1 skip traversal, 2 per-wave stamps, 4 every
     // group coarse, 8 coarse kernel on a side stream, 16 counted shadow walks
@@ -108,34 +91,9 @@ struct rt_camera {
     int pool_cap = kPoolCapMax;      // kOptPoolCap
     unsigned long long* d_dbg = nullptr;
     int64_t dbg_cap = 0;             // in u64
-    Hold hold;                       // the fine region renders keep (set_fine_region)
-    int32_t* d_order = nullptr;      // the current tile permutation (a slot's buffer)
-    int64_t order_key[kOrderKey] = {-1, -1, -1, -1, -1, -1, -1, -1, -1};
-    // Tile permutations live in a ring of slots: a new fine grid (a moving
-    // object changes it every frame) writes the next slot behind the
-    // caller's stream instead of rewriting the buffer earlier frames still
-    // read.  A slot is retired with an event on every stream that used it,
-    // and written again kOrderSlots grids later, once those have fired.
-    struct OrderSlot {
-        int32_t* d = nullptr;        // device permutation
-        int32_t* h = nullptr;        // pinned source of its upload
-        int64_t cap = 0;
-        hipEvent_t ev[8] = {};
-        int nev = 0;
-        bool device_sync = false;    // used by more streams than ev holds
-        // frames in flight: the upload's event and stream; a frame on
-        // another lane waits for it only when it renders with this slot
-        hipEvent_t up_ev = nullptr;
-        hipStream_t up_stream = nullptr;
-        bool up_valid = false;
-    } oslot[8];
-    int ocur = -1;
-    hipStream_t oused[8] = {};       // streams that launched with the current slot
-    int noused = 0;
-    bool oused_overflow = false;
+    TileOrder order;                 // tile dispatch orders, cost feedback, the held fine region
     int coarse = 8;                  // kOptCoarse: coarse groups per wave (0 = off)
     bool multiframe = false;         // inside rt_run_frames' multi-frame launches (auto_rays)
-    std::vector<int32_t> centre;     // centre-out permutation of the current fine grid (host copy)
     // 8x8 groups (x / 8, y / 8) holding a pixel whose primary ray has a zero
     // or tiny component (computed once, as the kernels compute the rays)
     std::vector<std::pair<int32_t, int32_t>> tiny_groups;
@@ -144,46 +102,6 @@ struct rt_camera {
     // (disjoint pixels), forked from and joined back into the caller's stream
     hipStream_t side = nullptr;
     hipEvent_t fork_ev = nullptr, join_ev = nullptr;
-    // tile order 3: each frame's per-unit pool iterations feed the next
-    // frames' dispatch order, read back asynchronously (never a sync).
-    // one buffer per stream that renders (cost_set): a sample copies the
-    // buffer of the stream that queues it, which only that stream's frames
-    // write, so frames in flight on other lanes (under motion, with another
-    // fine grid) never tear it
-    hipEvent_t slot_join_ev[8] = {};  // cost-order upload: joins the streams that read the slot
-    hipStream_t cost_up_stream = nullptr;   // the last cost-order upload's stream ...
-    bool cost_up_valid = false;             // ... while it may be pending
-    uint32_t* h_cost = nullptr;      // pinned: [tile][kCostSlots] pool iterations, written by a sampled frame
-    uint32_t* d_cost_host = nullptr; // its device address
-    int32_t* h_order = nullptr;      // pinned H2D source
-    int64_t host_cap = 0;            // tiles h_cost / h_order hold
-    hipEvent_t cost_ev = nullptr, order_ev = nullptr;
-    bool cost_pending = false, order_pending = false;
-    int frames_since = 0;
-    uint64_t layout_gen = 0, cost_gen = 0;   // fine-grid generation, and the one h_cost was read for
-    // The order ranks tiles by the cost of one wave per unit (pool
-    // iterations).  Split halves report an estimate, so each tile's cost as
-    // last measured unsplit is remembered (per grid) and used while it
-    // renders split: sample_split holds, per tile, whether the sampled frame
-    // rendered it split (taken when the sample is queued).
-    std::vector<uint8_t> sample_split;
-    std::vector<uint32_t> cost_mem;
-    uint64_t mem_gen = ~0ull;
-    uint64_t order_gen = ~0ull;              // generation whose cost order d_order holds
-    int32_t order_split = 0;                 // split tiles at the head of that cost order
-    // the last cost orders of two grids (order_key): a camera that
-    // alternates between two tilings -- rt_run_frames' multi-frame rays rule
-    // against the per-frame one on a small frame -- starts each
-    // switch with the order it last measured there, not the centre order
-    struct KeptOrder {
-        int64_t key[kOrderKey] = {};
-        std::vector<int32_t> ord;
-        std::vector<uint32_t> mem;  // cost_mem with it
-        int32_t split = 0;
-    };
-    KeptOrder kept[2];
-    int kept_next = 0;
-    uint64_t restores = 0;           // kOptOrderRestores: kept orders restored
     int rays = 0;                    // kOptRays: pixels per wave of kernel 3 (0: auto_rays)
     int last_rays = 0;               // the pixels per wave the last kernel-3 render used
     int last_fast = 0;               // whether it took the kFast walks (fast_proof)
@@ -210,21 +128,43 @@ struct rt_camera {
     hipEvent_t tune_ev[2 * 12] = {};
     // Frame loops render the same (transform, tile, buffers) frame after
     // frame: its launch geometry is kept and reused while nothing it depends
-    // on changed (options, object, tree: geom_gen / tree_version).
+    // on changed.  The one rule: whatever changes an input of the geometry
+    // other than the key's own terms bumps geom_gen before a cache is next
+    // consulted -- rt_camera_set_option, the multi-frame rays rule
+    // (run_frames_multiframe), and prepare_camera_object, which every render
+    // and rt_frame_rect call first and which bumps it whenever the object or
+    // its tree (tree_version) is not the one it last prepared.  So the key
+    // carries no tree term, and rt_camera_add_object bumps nothing itself.
     uint64_t geom_gen = 1;
-    struct ParamCache {
+    struct GeomKey {
         bool valid = false;
-        uint64_t gen = 0, tree = 0;
+        uint64_t gen = 0;
         float xf[12];
         uint32_t mode = 0;
-        int32_t nranks = 0, rank = 0;
+        int32_t nranks = 0;
+        bool matches(uint64_t g, const float* x, uint32_t m, int32_t nr) const {
+            return valid && gen == g && mode == m && nranks == nr && !memcmp(xf, x, sizeof xf);
+        }
+        void set(uint64_t g, const float* x, uint32_t m, int32_t nr) {
+            valid = true;
+            gen = g;
+            memcpy(xf, x, sizeof xf);
+            mode = m;
+            nranks = nr;
+        }
+    };
+    struct ParamCache {
+        GeomKey key;
+        int32_t rank = 0;
         TraceParams p;               // its argb / hit are set per call
     } pcache;
     // rt_run_frames with frames in flight: the library's own render lanes
     // (and, with a gather, its comm lane), each a stream created after the
     // caller's, so on hardware queues of its own while queues are free.
     // While a loop runs, `active` lists the lanes frames are issued to: a
-    // cost-order upload then waits for all of them and they wait for it.
+    // timed trial frame of the shadow push order then waits for all of them
+    // and they wait for it (render_common).  (A cost-order upload waits for
+    // the streams that launched with its slot, which TileOrder records.)
     hipStream_t lanes[RT_LOOP_MAX_LANES + 1] = {};
     hipEvent_t lane_ev[RT_LOOP_MAX_LANES + 1] = {};
     int nactive = 0;
@@ -233,52 +173,12 @@ struct rt_camera {
     // warm-up call's), pairs bracketing sampled frames' renders
     std::vector<hipEvent_t> loop_ev;
     struct RectCache {
-        bool valid = false;
-        uint64_t gen = 0, tree = 0;
-        float xf[12];
-        uint32_t mode = 0;
-        int32_t nranks = 0;
+        GeomKey key;
         int32_t rect[4];
     } rcache;
 };
 
 namespace {
-
-struct DeviceGuard {
-    int prev = -1;
-    bool ok = false;
-    explicit DeviceGuard(int dev) {
-        if (hipGetDevice(&prev) != hipSuccess) prev = -1;
-        ok = hipSetDevice(dev) == hipSuccess;
-    }
-    ~DeviceGuard() {
-        if (prev >= 0) (void)hipSetDevice(prev);
-    }
-};
-
-int hip_check(hipError_t e, const char* what) {
-    if (e == hipSuccess) return RT_OK;
-    return fail(e == hipErrorOutOfMemory ? RT_ERR_NOMEM : RT_ERR_HIP, "%s: %s", what, hipGetErrorString(e));
-}
-
-template <class T>
-int dev_alloc(T** p, size_t count, const char* what) {
-    *p = nullptr;
-    if (count == 0) count = 1;
-    return hip_check(hipMalloc((void**)p, sizeof(T) * count), what);
-}
-
-template <class T>
-void dev_free(T*& p) {
-    if (p) (void)hipFree(p);
-    p = nullptr;
-}
-
-// The KD kernel a render runs.  Every kernel handles any tree the LDS stack
-// admits (height <= kMaxDepth; rt_scene_set_kd rejects taller ones): kernel
-// 3's marked path codes take height + 1 <= 25 bits.
-int effective_kernel(const rt_camera* c) { return c->kernel_version; }
-
 
 int prepare_camera_object(rt_camera* c) {
     rt_scene* s = c->obj;
@@ -343,462 +243,13 @@ int prepare_camera_object(rt_camera* c) {
     // kept cost orders measured another object or tree: a grid
     // of the same key must not restart from them (the camera's position is
     // fixed at rt_camera_create, so this covers every input of a cost order)
-    for (auto& e : c->kept) e = rt_camera::KeptOrder();
-    c->kept_next = 0;
+    c->order.forget_kept();
     c->prepared_version = s->tree_version + 1;
-    return RT_OK;
-}
-
-// Centre-out permutation of the launch's tiles: blocks are dispatched in
-// index order, so the expensive tiles (the object sits mid-frame) start
-// first and the cheap background tiles fill in behind them.
-constexpr int kOrderSlots = 8;
-constexpr int kCostPeriod = 16;  // frames between cost samples (tile order 3)
-
-// The current slot was launched with on `st`.
-void note_order_stream(rt_camera* c, hipStream_t st) {
-    for (int i = 0; i < c->noused; i++)
-        if (c->oused[i] == st) return;
-    if (c->noused < 8) c->oused[c->noused++] = st;
-    else c->oused_overflow = true;
-}
-
-// Tiles of this rank's whole frame in p's tiling: the most any fine grid of
-// this camera and tiling holds.  Order slots and cost buffers are sized for
-// it, so a moving object's growing grid never reallocates them (each
-// reallocation freed device memory, a device-wide synchronisation, and
-// re-pinned host memory).
-int64_t all_tiles(const rt_camera* c, const TraceParams& p) {
-    if (c->debug & 64) return 0;  // A/B: sized for the current grid only
-    return (int64_t)((c->w + p.tile_w - 1) / p.tile_w) * p.nslots * (kTileH / p.tile_h);
-}
-
-int ensure_order(rt_camera* c, const TraceParams& p, hipStream_t st) {
-    // (the rays per wave too: 16- and 32-ray units both tile 8 x 8, and a cost
-    // order measured with one is kept for it, keep_order / restore_order)
-    const int64_t key[kOrderKey] = {p.tile_w, p.tile_h, p.tiles_x, p.block_rows, p.nranks,
-                                    p.rank, p.fine_tx0, p.fine_s0, p.rays};
-    if (std::equal(key, key + kOrderKey, c->order_key)) return RT_OK;
-    const int64_t n = (int64_t)p.tiles_x * p.block_rows;
-    const int64_t per_band = kTileH / p.tile_h;
-    // centre-out: a counting sort of the tiles by their distance from the
-    // frame centre in 2-pixel rings, index order within a ring (O(n): a
-    // moving object changes the grid every frame, and a comparison sort of
-    // the 13k tiles of a 1080p frame took ~0.3 ms of host time per frame)
-    std::vector<int32_t> order((size_t)n), ring((size_t)n);
-    const double cx = 0.5 * c->w, cy = 0.5 * c->h;
-    const int32_t nring = (int32_t)(0.5 * std::sqrt(cx * cx + cy * cy)) + 2;
-    std::vector<int32_t> start((size_t)nring + 1, 0);
-    // row by row, the column terms once (a moving object recomputes this
-    // every frame: four 64-bit divisions per tile cost ~100 us of host time
-    // per 1080p frame)
-    std::vector<double> dx2((size_t)p.tiles_x);
-    for (int64_t c0 = 0; c0 < p.tiles_x; c0++) {
-        const double x = ((c0 + p.fine_tx0) + 0.5) * p.tile_w;
-        dx2[(size_t)c0] = (x - cx) * (x - cx);
-    }
-    for (int64_t row = 0, t = 0; row < p.block_rows; row++) {
-        const int64_t slot = row / per_band + p.fine_s0, yin = (row % per_band) * p.tile_h;
-        const double y = (double)((p.rank + slot * (int64_t)p.nranks) * kTileH + yin) + 0.5 * p.tile_h;
-        const double dy2 = (y - cy) * (y - cy);
-        for (int64_t c0 = 0; c0 < p.tiles_x; c0++, t++) {
-            const int32_t k = std::min(nring - 1, (int32_t)(0.5 * std::sqrt(dx2[(size_t)c0] + dy2)));
-            ring[(size_t)t] = k;
-            start[(size_t)k + 1]++;
-        }
-    }
-    for (int32_t k = 0; k < nring; k++) start[(size_t)k + 1] += start[(size_t)k];
-    for (int64_t t = 0; t < n; t++) order[(size_t)start[(size_t)ring[(size_t)t]]++] = (int32_t)t;
-    int rc;
-    // retire the current slot: an event on each stream that launched with it
-    // (a pending cost-order upload into it was issued on one of them)
-    if (c->ocur >= 0) {
-        auto& o = c->oslot[c->ocur];
-        o.nev = 0;
-        o.device_sync = c->oused_overflow;
-        for (int i = 0; i < c->noused && !o.device_sync; i++) {
-            if (!o.ev[i] && (rc = hip_check(hipEventCreateWithFlags(&o.ev[i], hipEventDisableTiming), "order event")))
-                return rc;
-            if ((rc = hip_check(hipEventRecord(o.ev[i], c->oused[i]), "order retire"))) return rc;
-            o.nev++;
-        }
-    }
-    c->noused = 0;
-    c->oused_overflow = false;
-    // the next slot, once every launch that read it (and its upload) is done
-    const int sl = (c->ocur + 1) % kOrderSlots;
-    auto& o = c->oslot[sl];
-    if (o.device_sync) rc = hip_check(hipDeviceSynchronize(), "order slot sync");
-    for (int i = 0; !rc && i < o.nev; i++) rc = hip_check(hipEventSynchronize(o.ev[i]), "order slot wait");
-    if (rc) return rc;
-    o.nev = 0;
-    o.device_sync = false;
-    if (o.cap < n) {
-        const int64_t want = std::max(n, all_tiles(c, p));
-        dev_free(o.d);
-        if (o.h) (void)hipHostFree(o.h);
-        o.h = nullptr;
-        o.cap = 0;
-        if ((rc = dev_alloc(&o.d, (size_t)want, "hipMalloc(order)")) ||
-            (rc = hip_check(hipHostMalloc((void**)&o.h, sizeof(int32_t) * (size_t)want, 0), "hipHostMalloc(order)")))
-            return rc;
-        o.cap = want;
-    }
-    std::copy(order.begin(), order.end(), o.h);
-    if ((rc = hip_check(hipMemcpyAsync(o.d, o.h, sizeof(int32_t) * (size_t)n, hipMemcpyHostToDevice, st), "H2D order")))
-        return rc;
-    // frames in flight on other lanes that render with this slot wait for
-    // the upload (order_wait); a moving object's next grid, on the other
-    // lane, has a slot of its own and does not (a wait on every lane here
-    // tied each lane's next frame to the other's previous one)
-    // (always recorded: a caller that renders on several streams of its own
-    // needs the wait as much as the library's lanes do)
-    o.up_valid = false;
-    if (!o.up_ev && (rc = hip_check(hipEventCreateWithFlags(&o.up_ev, hipEventDisableTiming), "order event")))
-        return rc;
-    if ((rc = hip_check(hipEventRecord(o.up_ev, st), "order upload event"))) return rc;
-    o.up_stream = st;
-    o.up_valid = true;
-    c->cost_up_valid = false;  // a cost order of the previous slot
-    c->ocur = sl;
-    c->d_order = o.d;
-    c->order_gen = ~0ull;  // no cost order for this grid yet
-    c->order_split = 0;    // nor split tiles
-    std::copy(key, key + kOrderKey, c->order_key);
-    c->centre.swap(order);
-    c->layout_gen++;
-    // tile order 3: sample the new grid's costs once it has held for two
-    // frames (a moving object changes it every frame; its samples would
-    // always be stale)
-    c->frames_since = kCostPeriod - 2;
     return RT_OK;
 }
 
 constexpr int kAnyOrders = 4, kTuneReps = 3, kTuneTrials = kAnyOrders * kTuneReps;
 constexpr int kTunePeriod = 2048;  // frames between timing rounds of the shadow push order
-
-// Buffers of tile order 3 for n fine tiles (allocated when the grid grows).
-int ensure_cost(rt_camera* c, int64_t n) {
-    int rc;
-    if (c->host_cap < n) {
-        // copies in flight may still use the pinned buffers
-        if (c->cost_pending) (void)hipEventSynchronize(c->cost_ev);
-        if (c->order_pending) (void)hipEventSynchronize(c->order_ev);
-        if (c->h_cost) (void)hipHostFree(c->h_cost);
-        if (c->h_order) (void)hipHostFree(c->h_order);
-        c->h_cost = nullptr;
-        c->d_cost_host = nullptr;
-        c->h_order = nullptr;
-        c->host_cap = 0;
-        c->cost_pending = c->order_pending = false;
-        if ((rc = hip_check(hipHostMalloc((void**)&c->h_cost, sizeof(uint32_t) * kCostSlots * (size_t)n, 0), "hipHostMalloc(cost)")) ||
-            (rc = hip_check(hipHostMalloc((void**)&c->h_order, sizeof(int32_t) * (size_t)n, 0), "hipHostMalloc(order)")) ||
-            (rc = hip_check(hipHostGetDevicePointer((void**)&c->d_cost_host, c->h_cost, 0), "cost device pointer")))
-            return rc;
-        c->host_cap = n;
-    }
-    if (!c->cost_ev && (rc = hip_check(hipEventCreateWithFlags(&c->cost_ev, hipEventDisableTiming), "cost event")))
-        return rc;
-    if (!c->order_ev && (rc = hip_check(hipEventCreateWithFlags(&c->order_ev, hipEventDisableTiming), "order event")))
-        return rc;
-    return RT_OK;
-}
-
-// Dispatch order from the sampled costs (pool iterations of each tile's
-// waves).  Order 3: heaviest tile first (counting sort, stable over the
-// centre-out order).  Order 4: the tiles in Morton order are cut into 8 runs
-// of equal total cost, one per XCD (blocks b and b + 8 share an XCD), each
-// run heaviest first, interleaved so block b takes the next tile of run b % 8:
-// the XCDs finish together and each L2 serves one screen region's subtrees.
-// Order 5 (round 6, verdict r05 item 5): order 0's XCD mapping (8 runs of
-// equal tile count, contiguous in row-major order: each XCD a band of the
-// fine region's rows), each run heaviest first, interleaved the same way.
-// Multi-frame launches pad every frame's grid to a multiple of 8 blocks for
-// orders 0, 4 and 5 (render_common), so block b of every frame lands on XCD
-// b % 8; these orders render no split tiles.
-std::vector<int32_t> cost_order(const rt_camera* c, const TraceParams& p, int xcd_mode, const uint32_t* cost) {
-    const bool xcd_split = xcd_mode != 0;
-    const int64_t n = (int64_t)p.tiles_x * p.block_rows;
-    uint32_t mx = 0;
-    auto wave_max = [&](int64_t t) {
-        uint32_t m = 0;
-        for (int k = 0; k < kCostSlots; k++) m = std::max(m, cost[kCostSlots * (size_t)t + k]);
-        return m;
-    };
-    auto wave_sum = [&](int64_t t) {
-        double m = 0;
-        for (int k = 0; k < kCostSlots; k++) m += cost[kCostSlots * (size_t)t + k];
-        return m;
-    };
-    for (int64_t t = 0; t < n; t++) mx = std::max(mx, wave_max(t));
-    mx = std::min<uint32_t>(mx, 1u << 16);
-    auto cost_of = [&](int32_t t) { return std::min<uint32_t>(wave_max(t), mx); };
-    // stable counting sort of `in` by cost, descending, appended to `out`
-    std::vector<int64_t> start((size_t)mx + 2);
-    auto sort_desc = [&](const int32_t* in, int64_t m, int32_t* out) {
-        std::fill(start.begin(), start.end(), 0);
-        for (int64_t k = 0; k < m; k++) start[(size_t)(mx - cost_of(in[k])) + 1]++;
-        for (size_t k = 1; k < start.size(); k++) start[k] += start[k - 1];
-        for (int64_t k = 0; k < m; k++) out[start[(size_t)(mx - cost_of(in[k]))]++] = in[k];
-    };
-    std::vector<int32_t> ord((size_t)n);
-    if (!xcd_split) {
-        sort_desc(c->centre.data(), n, ord.data());
-        return ord;
-    }
-    // Morton order of the tiles (pixel-proportional coordinates)
-    std::vector<std::pair<uint64_t, int32_t>> mk((size_t)n);
-    auto spread = [](uint64_t v) {
-        v &= 0xFFFFFFFFull;
-        v = (v | (v << 16)) & 0x0000FFFF0000FFFFull;
-        v = (v | (v << 8)) & 0x00FF00FF00FF00FFull;
-        v = (v | (v << 4)) & 0x0F0F0F0F0F0F0F0Full;
-        v = (v | (v << 2)) & 0x3333333333333333ull;
-        v = (v | (v << 1)) & 0x5555555555555555ull;
-        return v;
-    };
-    for (int64_t t = 0; t < n; t++) {
-        const uint64_t x = (uint64_t)(t % p.tiles_x) * (uint64_t)p.tile_w, y = (uint64_t)(t / p.tiles_x) * (uint64_t)p.tile_h;
-        // order 5: row-major (the tile index itself)
-        mk[(size_t)t] = {xcd_mode == 2 ? (uint64_t)t : (spread(x) | (spread(y) << 1)), (int32_t)t};
-    }
-    std::sort(mk.begin(), mk.end());
-    double total = 0.0;
-    for (int64_t t = 0; t < n; t++) total += 1.0 + wave_sum(t);
-    constexpr int kXcd = 8;
-    std::vector<int32_t> runs((size_t)n);
-    int64_t cut[kXcd + 1] = {0};
-    int r = 1;
-    if (xcd_mode == 2) {
-        // equal tile counts: block b (XCD b % 8) takes tile k = b / 8 of run
-        // b % 8, as order 0 does
-        for (; r < kXcd; r++) cut[r] = (n * r) / kXcd;
-    } else {
-        double acc = 0.0;
-        for (int64_t k = 0; k < n && r < kXcd; k++) {
-            const int32_t t = mk[(size_t)k].second;
-            acc += 1.0 + wave_sum(t);
-            while (r < kXcd && acc >= total * r / kXcd) cut[r++] = k + 1;
-        }
-    }
-    while (r <= kXcd) cut[r++] = n;
-    std::vector<int32_t> in((size_t)n);
-    for (int64_t k = 0; k < n; k++) in[(size_t)k] = mk[(size_t)k].second;
-    for (int x = 0; x < kXcd; x++) sort_desc(in.data() + cut[x], cut[x + 1] - cut[x], runs.data() + cut[x]);
-    int64_t pos[kXcd];
-    for (int x = 0; x < kXcd; x++) pos[x] = cut[x];
-    for (int64_t b = 0; b < n; b++) {
-        int x = (int)(b % kXcd);
-        if (pos[x] == cut[x + 1]) {  // run exhausted: the run with most tiles left
-            int best = -1;
-            for (int y = 0; y < kXcd; y++)
-                if (pos[y] < cut[y + 1] && (best < 0 || cut[y + 1] - pos[y] > cut[best + 1] - pos[best])) best = y;
-            x = best;
-        }
-        ord[(size_t)b] = runs[(size_t)pos[x]++];
-    }
-    return ord;
-}
-
-// After a tile-order-3 frame: when an earlier cost sample has arrived, order
-// the tiles by it (heaviest unit first, centre-out among equals) and upload
-// the order behind this frame.  Every kCostPeriod frames one frame is the
-// sample: its kernel writes its units' costs straight into pinned host memory
-// (cost_sample_now / c->h_cost; no copy kernel, and the other frames write
-// no costs), and an event after it says when the sample has arrived.
-// Non-blocking (events are only queried); skipped while the stream is being
-// captured into a graph.
-// Grids of fewer than this many 16-ray tiles (4 units each) split the tiles
-// above RT_SPLIT_PCT % of the heaviest, larger ones only those above
-// RT_SPLIT_PCT_LARGE %: at 1080p (3.4k tiles) splitting half the top measured
-// slower with two frames in flight (dragon 16.2k -> 15.6k FPS, knot 10.19k ->
-// 10.08k), at 960x540 (850 tiles) much faster (dragon 33.7k -> 44.5k, r03g).
-#ifndef RT_SPLIT_MAX_TILES
-#define RT_SPLIT_MAX_TILES 2048
-#endif
-constexpr int64_t kSplitMaxTiles = RT_SPLIT_MAX_TILES;
-// which tiles split: cost > RT_SPLIT_PCT % of the top, at most n / RT_SPLIT_CAP_DIV
-#ifndef RT_SPLIT_PCT
-#define RT_SPLIT_PCT 50
-#endif
-// grids of kSplitMaxTiles or more: only tiles above RT_SPLIT_PCT_LARGE % of
-// the top (with deterministic split costs, r03zf: dragon 1080p solo 74.0 ->
-// 71.7 us, knot 107.1 -> 104.7 us, FPS unchanged; 0: no split there)
-#ifndef RT_SPLIT_PCT_LARGE
-#define RT_SPLIT_PCT_LARGE 75
-#endif
-#ifndef RT_SPLIT_CAP_DIV
-#define RT_SPLIT_CAP_DIV 4
-#endif
-// 8-ray units split into 4-pixel halves as well (with two-level iterations:
-// ranks of 8 at 1080p, dragon 16.8-19.4 -> 16.3-19.0 us per rank, knot max
-// 26.7 -> 21.9 us, r03z)
-#ifndef RT_SPLIT8
-#define RT_SPLIT8 1
-#endif
-
-// Whether the frame about to launch on `st` is a cost sample: its kernel then
-// writes its units' costs into c->h_cost (zeroed here) instead of nothing.
-bool cost_sample_now(rt_camera* c, hipStream_t st) {
-    if (c->cost_pending || c->frames_since + 1 < kCostPeriod || !c->h_cost) return false;
-    hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
-    if (hipStreamIsCapturing(st, &cs) == hipSuccess && cs != hipStreamCaptureStatusNone) return false;
-    return true;
-}
-
-void keep_order(rt_camera* c, const std::vector<int32_t>& ord, int32_t split) {
-    rt_camera::KeptOrder* k = nullptr;
-    for (auto& e : c->kept)
-        if (std::equal(e.key, e.key + kOrderKey, c->order_key)) k = &e;
-    if (!k) {
-        k = &c->kept[c->kept_next];
-        c->kept_next ^= 1;
-    }
-    std::copy(c->order_key, c->order_key + kOrderKey, k->key);
-    k->ord = ord;
-    k->mem = c->cost_mem;
-    k->split = split;
-}
-
-// A fresh grid (no cost order yet) that held a cost order before: upload it
-// (on st, behind ensure_order's centre order; frames on other streams wait
-// for it as for cost_feedback's uploads).
-int restore_order(rt_camera* c, const TraceParams& p, hipStream_t st) {
-    const int64_t n = (int64_t)p.tiles_x * p.block_rows;
-    if (c->order_gen == c->layout_gen || n > c->host_cap) return RT_OK;
-    // the previous grid's last cost-order upload reads h_order: wait for it
-    // by query only (cost_feedback clears the flag at its next sample)
-    if (c->order_pending) {
-        if (hipEventQuery(c->order_ev) != hipSuccess) return RT_OK;
-        c->order_pending = false;
-    }
-    hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
-    if (hipStreamIsCapturing(st, &cs) == hipSuccess && cs != hipStreamCaptureStatusNone) return RT_OK;
-    const rt_camera::KeptOrder* k = nullptr;
-    for (const auto& e : c->kept)
-        if ((int64_t)e.ord.size() == n && std::equal(e.key, e.key + kOrderKey, c->order_key)) k = &e;
-    if (!k || c->noused > 0) return RT_OK;  // (only before the grid's first launch)
-    std::copy(k->ord.begin(), k->ord.end(), c->h_order);
-    int rc;
-    if ((rc = hip_check(hipMemcpyAsync(c->d_order, c->h_order, sizeof(int32_t) * (size_t)n, hipMemcpyHostToDevice, st),
-                        "H2D kept cost order")) ||
-        (rc = hip_check(hipEventRecord(c->order_ev, st), "order event")))
-        return rc;
-    c->cost_up_stream = st;
-    c->cost_up_valid = true;
-    c->order_pending = true;
-    c->order_split = k->split;
-    c->order_gen = c->layout_gen;
-    c->restores++;
-    if ((int64_t)k->mem.size() == n) {
-        c->cost_mem = k->mem;
-        c->mem_gen = c->layout_gen;
-    }
-    return RT_OK;
-}
-
-int cost_feedback(rt_camera* c, const TraceParams& p, void* stream, bool sampled) {
-    hipStream_t st = (hipStream_t)stream;
-    hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
-    if (hipStreamIsCapturing(st, &cs) == hipSuccess && cs != hipStreamCaptureStatusNone) return RT_OK;
-    const int64_t n = (int64_t)p.tiles_x * p.block_rows;
-    if (c->cost_pending) {
-        if (hipEventQuery(c->cost_ev) != hipSuccess) return RT_OK;
-        if (c->order_pending && hipEventQuery(c->order_ev) != hipSuccess) return RT_OK;
-        c->cost_pending = c->order_pending = false;
-        c->frames_since = 0;
-        if (c->cost_gen != c->layout_gen || (int64_t)c->centre.size() != n) return RT_OK;  // stale sample
-        // the sampled costs, with the remembered unsplit cost of each tile the
-        // sampled frame rendered split (a half reports an estimate)
-        if (c->mem_gen != c->layout_gen || (int64_t)c->cost_mem.size() != n) {
-            c->cost_mem.assign((size_t)n, 0u);
-            c->mem_gen = c->layout_gen;
-        }
-        std::vector<uint32_t> eff(c->h_cost, c->h_cost + kCostSlots * (size_t)n);
-        const bool have_flags = (int64_t)c->sample_split.size() == n;
-        for (int64_t t = 0; t < n; t++) {
-            uint32_t* e = eff.data() + kCostSlots * (size_t)t;
-            uint32_t m = 0;
-            for (int k = 0; k < kCostSlots; k++) m = std::max(m, e[k]);
-            const uint8_t mode = have_flags ? c->sample_split[(size_t)t] : 0;
-            if (mode && c->cost_mem[(size_t)t] > 0) {
-                for (int k = 0; k < kCostSlots; k++) e[k] = 0u;
-                e[0] = c->cost_mem[(size_t)t];
-            } else if (!mode) {
-                c->cost_mem[(size_t)t] = m;
-            }
-        }
-        const std::vector<int32_t> ord = cost_order(c, p, c->tile_order == 4 ? 1 : c->tile_order == 5 ? 2 : 0, eff.data());
-        bool same = true;
-        for (int64_t k = 0; k < n; k++) {
-            same = same && c->h_order[k] == ord[(size_t)k];
-            c->h_order[k] = ord[(size_t)k];
-        }
-        // Split tiles (order 3, 16-ray units): the tiles costlier than half
-        // the heaviest render as two 8-ray halves, so the heaviest chains
-        // end near the unsplit ones' (a unit's chain is mostly its items:
-        // half the rays, about half the pool iterations); at most a quarter
-        // of the tiles.  Debug bit 512: none.
-        int32_t split = 0;
-        auto cost_of = [&](int64_t t) {
-            uint32_t m = 0;
-            for (int k = 0; k < kCostSlots; k++) m = std::max(m, eff[kCostSlots * (size_t)t + k]);
-            return m;
-        };
-        const uint32_t top = n > 0 ? cost_of(ord[0]) : 0;
-        if (c->tile_order == 3 && (p.rays == 16 || (p.rays == 8 && RT_SPLIT8)) && kd3_waves(p.rays) == 4 &&
-            !(c->debug & 512) && n > 0 && (n < kSplitMaxTiles || RT_SPLIT_PCT_LARGE > 0)) {
-            const uint64_t pct = n < kSplitMaxTiles ? RT_SPLIT_PCT : RT_SPLIT_PCT_LARGE;
-            while (split < n / RT_SPLIT_CAP_DIV && 100ull * cost_of(ord[(size_t)split]) > pct * top && top >= 24)
-                split++;
-        }
-        same = same && split == c->order_split;
-        if (same && c->order_gen == c->layout_gen) return RT_OK;  // d_order already holds it
-        int rc;
-        // frames on other streams (frames in flight on the library's lanes,
-        // or a caller's own streams) read d_order: the upload waits for every
-        // stream that launched with this slot, and a later frame on another
-        // stream waits for the upload (render_common)
-        if (c->oused_overflow && (rc = hip_check(hipDeviceSynchronize(), "cost order sync"))) return rc;
-        for (int i = 0; i < c->noused && !c->oused_overflow; i++) {
-            if (c->oused[i] == st) continue;
-            if (!c->slot_join_ev[i] &&
-                (rc = hip_check(hipEventCreateWithFlags(&c->slot_join_ev[i], hipEventDisableTiming), "join event")))
-                return rc;
-            if ((rc = hip_check(hipEventRecord(c->slot_join_ev[i], c->oused[i]), "slot join")) ||
-                (rc = hip_check(hipStreamWaitEvent(st, c->slot_join_ev[i], 0), "slot join wait")))
-                return rc;
-        }
-        if ((rc = hip_check(hipMemcpyAsync(c->d_order, c->h_order, sizeof(int32_t) * (size_t)n, hipMemcpyHostToDevice, st),
-                            "H2D cost order")) ||
-            (rc = hip_check(hipEventRecord(c->order_ev, st), "order event")))
-            return rc;
-        c->cost_up_stream = st;
-        c->cost_up_valid = true;
-        c->order_pending = true;
-        c->order_split = split;  // launches after this upload (stream order) use it
-        c->order_gen = c->layout_gen;
-        keep_order(c, ord, split);
-        return RT_OK;
-    }
-    if (!sampled) {
-        ++c->frames_since;
-        return RT_OK;
-    }
-    int rc;
-    if ((rc = hip_check(hipEventRecord(c->cost_ev, st), "cost event"))) return rc;
-    c->cost_pending = true;
-    c->cost_gen = c->layout_gen;
-    // which tiles the order this frame launched with rendered split
-    // (render_common: order[0..split))
-    c->sample_split.assign((size_t)n, 0);
-    if (c->order_gen == c->layout_gen)
-        for (int32_t k = 0; k < p.split && k < n; k++) {
-            const int32_t t = c->h_order[k];
-            if (t >= 0 && t < n) c->sample_split[(size_t)t] = 1;
-        }
-    return RT_OK;
-}
 
 // Screen rectangle (inclusive pixel bounds, row 0 = bottom) that the root
 // box projects to, widened by a pixel.  Ray (ix, iy) points along
@@ -825,7 +276,7 @@ struct FrameGeom {
     // the camera's cached list, or computed by the caller
     const std::vector<std::pair<int32_t, int32_t>>* tiny = nullptr;
     // renders only (fill_params): the fine region the camera holds for this
-    // tiling (set_fine_region), or null for the exact region
+    // tiling (hold_region), or null for the exact region
     Hold* hold = nullptr;
     int32_t cam_flags = kCamUnordered;  // k_cam_nodes' flags of the camera's records (renders only)
 };
@@ -1179,22 +630,8 @@ have_rect:
     if (tx1 < tx0 || s1 < s0) {  // nothing of the box on this rank: all coarse
         tx0 = 0; tx1 = -1; s0 = 0; s1 = -1;
     } else if (c.hold && !p.plain_xf && !(c.debug & (4 | 256))) {
-        Hold& H = *c.hold;
         const int32_t key[6] = {p.tile_w, p.tile_h, p.nranks, p.rank, p.groups_x, p.nslots};
-        const int64_t area = (int64_t)(tx1 - tx0 + 1) * (s1 - s0 + 1);
-        const int64_t held = (int64_t)(H.tx1 - H.tx0 + 1) * (H.s1 - H.s0 + 1);
-        if (H.valid && std::equal(key, key + 6, H.key) && tx0 >= H.tx0 && tx1 <= H.tx1 && s0 >= H.s0 &&
-            s1 <= H.s1 && 2 * area >= held) {
-            tx0 = H.tx0; tx1 = H.tx1; s0 = H.s0; s1 = H.s1;
-        } else {
-            const int32_t ntx = (c.w + p.tile_w - 1) / p.tile_w;
-            const int32_t mx = std::max(2, (tx1 - tx0 + 1) / 8), ms = std::max(1, (s1 - s0 + 1) / 8);
-            tx0 = std::max(0, tx0 - mx); tx1 = std::min(ntx - 1, tx1 + mx);
-            s0 = std::max(0, s0 - ms); s1 = std::min(p.nslots - 1, s1 + ms);
-            H.valid = true;
-            std::copy(key, key + 6, H.key);
-            H.tx0 = tx0; H.tx1 = tx1; H.s0 = s0; H.s1 = s1;
-        }
+        hold_region(*c.hold, key, (c.w + p.tile_w - 1) / p.tile_w, p.nslots, tx0, tx1, s0, s1);
     }
     p.fine_tx0 = tx0;
     p.fine_s0 = s0;
@@ -1320,7 +757,7 @@ FrameGeom camera_geom(rt_camera* c) {
     g.v_mod = c->basis.v_mod;
     camera_relative_box(c->obj->root, c->pos, g.root_box);
     g.root_leaf = (c->obj->root_ref & kLeafBit) != 0;
-    g.kernel = effective_kernel(c);
+    g.kernel = c->kernel_version;
     g.rays = c->rays;
     g.multiframe = c->multiframe;
     g.coarse = c->coarse;
@@ -1333,7 +770,7 @@ FrameGeom camera_geom(rt_camera* c) {
 
 bool frame_geometry(rt_camera* c, const float* xform, const rt_tile* tile, uint32_t mode, TraceParams& p) {
     FrameGeom g = camera_geom(c);
-    g.hold = &c->hold;  // renders keep a held fine region (rt_frame_rect does not)
+    g.hold = &c->order.hold;  // renders keep a held fine region (rt_frame_rect does not)
     return frame_geometry(g, xform, tile, mode, p);
 }
 
@@ -1352,7 +789,7 @@ int fill_params(rt_camera* c, const float* xform, const rt_tile* tile, uint32_t*
     p.hit = hit;
     p.counters = c->d_counters;
     p.err = c->d_err;
-    const int kernel = mode == RT_MODE_KD ? effective_kernel(c) : 0;
+    const int kernel = mode == RT_MODE_KD ? c->kernel_version : 0;
     (void)frame_geometry(c, xform, tile, mode, p);
     p.root_ref = s->root_ref;
     p.ntri = s->ntri;
@@ -1361,7 +798,6 @@ int fill_params(rt_camera* c, const float* xform, const rt_tile* tile, uint32_t*
     // debug bit 1024: one-level iterations only
     p.two_depth = (c->debug & 1024) ? -1 : s->two_depth;
     p.tile_order = c->tile_order;
-    p.order = nullptr;
     p.split = 0;
     p.debug = c->debug;
     p.pool_cap = c->pool_cap;
@@ -1393,19 +829,7 @@ int fill_params(rt_camera* c, const float* xform, const rt_tile* tile, uint32_t*
         int rc = hip_check(hipMemset(c->d_dbg, 0, sizeof(uint64_t) * (size_t)need), "memset dbg");
         if (rc) return rc;
     }
-    p.cost = nullptr;
-    if (c->tile_order >= 2 && p.tiles_x * p.block_rows > 0) {
-        int rc = ensure_order(c, p, st);
-        if (rc) return rc;
-        p.order = c->d_order;
-        if (c->tile_order >= 3 && kernel == 3) {
-            if ((rc = ensure_cost(c, std::max<int64_t>(all_tiles(c, p), (int64_t)p.tiles_x * p.block_rows))) ||
-                (rc = restore_order(c, p, st)))
-                return rc;
-            p.cost = c->d_cost_host;  // (marks tile order 3; render_common passes it to sampled frames only)
-        }
-    }
-    return RT_OK;
+    return c->order.prepare(p, kernel, st, &p.order, &p.cost);
 }
 
 int check_tile(const rt_tile* tile) {
@@ -1740,7 +1164,6 @@ extern "C" int rt_camera_add_object(rt_camera* c, rt_scene* s) {
     DeviceGuard g(c->device);
     c->obj = s;
     c->prepared_version = 0;
-    c->geom_gen++;
     return prepare_camera_object(c);
 }
 
@@ -1790,7 +1213,7 @@ static int any_order_for(rt_camera* c, uint32_t flags, void* stream, int& trial)
 // earlier work, joined before its later work); measured slower, since its
 // waves take the slots the heaviest fine tiles need.
 static int launch_split(rt_camera* c, const TraceParams& p, uint32_t mode, uint32_t flags, void* stream) {
-    const int kernel = effective_kernel(c);
+    const int kernel = c->kernel_version;
     if (p.coarse_blocks == 0 || p.tiles_x * p.block_rows == 0 || !(c->debug & 8))
         return launch_trace(p, mode, flags, kernel, stream, kPartAll);
     int rc;
@@ -1901,9 +1324,9 @@ static int render_common(rt_camera* c, const float* xform, uint32_t mode, uint32
         return fail(RT_ERR_INVALID, "rt_render: unknown flags 0x%x", flags);
     if (flags & RT_FLAG_SHADOW) {
         if (mode != RT_MODE_KD) return fail(RT_ERR_INVALID, "rt_render: RT_FLAG_SHADOW needs RT_MODE_KD");
-        if (effective_kernel(c) != 3)
+        if (c->kernel_version != 3)
             return fail(RT_ERR_STATE, "rt_render: shadow rays run in the wave-cooperative kernel (3); kernel %d",
-                        effective_kernel(c));
+                        c->kernel_version);
     }
     static const float ident[12] = {1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1, 0};
     const float* xf = xform ? xform : ident;
@@ -1926,19 +1349,14 @@ static int render_common(rt_camera* c, const float* xform, uint32_t mode, uint32
     }
     auto& pc = c->pcache;
     TraceParams p;
-    if (pc.valid && !(c->debug & 2) && pc.gen == c->geom_gen && pc.tree == c->obj->tree_version && pc.mode == mode &&
-        pc.nranks == nr && pc.rank == rk && !memcmp(pc.xf, xf, sizeof pc.xf)) {
+    if (!(c->debug & 2) && pc.key.matches(c->geom_gen, xf, mode, nr) && pc.rank == rk) {
         p = pc.p;  // the same frame as the last one: its geometry stands
         p.argb = argb;
         p.hit = hit;
     } else {
         if ((rc = fill_params(c, xform, tile, argb, hit, mode, p, (hipStream_t)stream))) return rc;
-        pc.valid = !(c->debug & 2);
-        pc.gen = c->geom_gen;
-        pc.tree = c->obj->tree_version;
-        memcpy(pc.xf, xf, sizeof pc.xf);
-        pc.mode = mode;
-        pc.nranks = nr;
+        pc.key.set(c->geom_gen, xf, mode, nr);
+        pc.key.valid = !(c->debug & 2);
         pc.rank = rk;
         pc.p = p;
     }
@@ -1957,7 +1375,7 @@ static int render_common(rt_camera* c, const float* xform, uint32_t mode, uint32
         const int64_t npair = (c->obj->ntri + 1) / 2;
         if (p.flat_chunks > npair) p.flat_chunks = (int32_t)npair;
     }
-    if (mode == RT_MODE_KD && effective_kernel(c) == 3) {
+    if (mode == RT_MODE_KD && c->kernel_version == 3) {
         c->last_rays = p.rays;
         // bit 0: the nearest-hit walk's proof, bit 1: the shadow walk's (a
         // shadow render), bit 2: under an object transform
@@ -1978,28 +1396,14 @@ static int render_common(rt_camera* c, const float* xform, uint32_t mode, uint32
             return rc;
     }
     if (trial >= 0 && (rc = hip_check(hipEventRecord(c->tune_ev[2 * trial], st), "order trial start"))) return rc;
-    // a slot (or its cost order) uploaded on another stream: this frame's
-    // launch waits for it (no barrier packet once the upload has landed)
-    for (int k = 0; p.order && k < kOrderSlots; k++) {
-        auto& o = c->oslot[k];
-        if (o.d != p.order || !o.up_valid || o.up_stream == st) continue;
-        if (hipEventQuery(o.up_ev) == hipSuccess) o.up_valid = false;
-        else if ((rc = hip_check(hipStreamWaitEvent(st, o.up_ev, 0), "order upload wait"))) return rc;
-    }
-    if (p.order && p.order == c->d_order && c->cost_up_valid && c->cost_up_stream != st) {
-        if (hipEventQuery(c->order_ev) == hipSuccess) c->cost_up_valid = false;
-        else if ((rc = hip_check(hipStreamWaitEvent(st, c->order_ev, 0), "cost order wait"))) return rc;
-    }
-    // split tiles of the cost order in d_order (launches are stream-ordered
-    // behind its upload; other streams wait for it above)
-    p.split = (p.order && p.order == c->d_order && p.cost && (p.rays == 16 || (p.rays == 8 && RT_SPLIT8)) &&
-               !(c->debug & 512)) ? c->order_split : 0;
     const bool order3 = p.cost != nullptr;
     // a multi-frame launch (KD kernel 3, fused far fill, no per-frame
     // outputs beyond the frame): one launch for pf->frames frames, no cost
     // sample inside it
-    const bool persist = pf && pf->frames > 1 && mode == RT_MODE_KD && effective_kernel(c) == 3 && p.coarse_blocks == 0 &&
+    const bool persist = pf && pf->frames > 1 && mode == RT_MODE_KD && c->kernel_version == 3 && p.coarse_blocks == 0 &&
                          flags == 0 && !display;
+    bool sampled = false;
+    if ((rc = c->order.before_launch(p, st, persist, &sampled))) return rc;
     p.pf_frames = 0;
     if (persist) {
         p.pf_blocks = (int32_t)fine_grid_blocks(p);
@@ -2018,20 +1422,7 @@ static int render_common(rt_camera* c, const float* xform, uint32_t mode, uint32
         for (int k = 0; k < RT_LOOP_MAX_BUF; k++) p.pf_argb[k] = k < pf->nbuf ? pf->argb[k] : nullptr;
         if (rendered) *rendered = p.pf_frames;
     }
-    const bool sampled = order3 && !persist && cost_sample_now(c, st);
-    if (sampled) {
-        p.cost = c->d_cost_host;
-        // the kernel writes this frame's costs into the pinned host buffer;
-        // slots a tile does not write (missing waves) read 0
-        memset(c->h_cost, 0, sizeof(uint32_t) * kCostSlots * (size_t)p.tiles_x * p.block_rows);
-    } else {
-        p.cost = nullptr;
-    }
     if ((rc = launch_split(c, p, mode, flags, stream))) return rc;
-    if (p.order) {  // the streams that read the current order slot
-        note_order_stream(c, st);
-        if ((c->debug & 8) && c->side) note_order_stream(c, c->side);
-    }
     if (trial >= 0) {
         if ((rc = hip_check(hipEventRecord(c->tune_ev[2 * trial + 1], st), "order trial stop"))) return rc;
         c->tune_pending = c->tune_next == kTuneTrials;
@@ -2040,7 +1431,7 @@ static int render_common(rt_camera* c, const float* xform, uint32_t mode, uint32
                 (rc = hip_check(hipStreamWaitEvent(c->active[l], c->tune_ev[2 * trial + 1], 0), "trial fork wait")))
                 return rc;
     }
-    return order3 ? cost_feedback(c, p, stream, sampled) : RT_OK;
+    return c->order.after_launch(p, st, (c->debug & 8) ? c->side : nullptr, order3, sampled);
 }
 
 extern "C" int rt_render(rt_camera* c, const float* xform, uint32_t mode, uint32_t flags, const rt_tile* tile,
@@ -2139,19 +1530,13 @@ extern "C" int rt_frame_rect(rt_camera* c, const float* xform, uint32_t mode, in
     static const float ident[12] = {1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1, 0};
     const float* xf = xform ? xform : ident;
     auto& rcx = c->rcache;
-    if (rcx.valid && rcx.gen == c->geom_gen && rcx.tree == c->obj->tree_version && rcx.mode == mode &&
-        rcx.nranks == nranks && !memcmp(rcx.xf, xf, sizeof rcx.xf)) {
+    if (rcx.key.matches(c->geom_gen, xf, mode, nranks)) {
         memcpy(rect, rcx.rect, sizeof rcx.rect);
         return RT_OK;
     }
     rc = frame_rect_uncached(c, xform, mode, nranks, rect);
     if (rc) return rc;
-    rcx.valid = true;
-    rcx.gen = c->geom_gen;
-    rcx.tree = c->obj->tree_version;
-    memcpy(rcx.xf, xf, sizeof rcx.xf);
-    rcx.mode = mode;
-    rcx.nranks = nranks;
+    rcx.key.set(c->geom_gen, xf, mode, nranks);
     memcpy(rcx.rect, rect, sizeof rcx.rect);
     return RT_OK;
 }
@@ -2433,24 +1818,10 @@ extern "C" void rt_camera_destroy(rt_camera* c) {
     dev_free(c->d_split);
     dev_free(c->d_rec);
     dev_free(c->d_tpair);
-    for (auto& o : c->oslot) {
-        dev_free(o.d);
-        if (o.h) (void)hipHostFree(o.h);
-        for (hipEvent_t e : o.ev)
-            if (e) (void)hipEventDestroy(e);
-        if (o.up_ev) (void)hipEventDestroy(o.up_ev);
-    }
-    c->d_order = nullptr;
     dev_free(c->d_dbg);
     for (auto& k : c->flat_keys) dev_free(k.d);
-    for (hipEvent_t e : c->slot_join_ev)
-        if (e) (void)hipEventDestroy(e);
-    if (c->h_cost) (void)hipHostFree(c->h_cost);
-    if (c->h_order) (void)hipHostFree(c->h_order);
-    if (c->cost_ev) (void)hipEventDestroy(c->cost_ev);
     for (hipEvent_t e : c->tune_ev)
         if (e) (void)hipEventDestroy(e);
-    if (c->order_ev) (void)hipEventDestroy(c->order_ev);
     if (c->fork_ev) (void)hipEventDestroy(c->fork_ev);
     if (c->join_ev) (void)hipEventDestroy(c->join_ev);
     for (hipEvent_t e : c->loop_ev)
@@ -2460,7 +1831,7 @@ extern "C" void rt_camera_destroy(rt_camera* c) {
         if (c->lanes[k]) (void)hipStreamDestroy(c->lanes[k]);
         if (c->lane_ev[k]) (void)hipEventDestroy(c->lane_ev[k]);
     }
-    delete c;
+    delete c;  // (its TileOrder frees its own, under the guard)
 }
 
 extern "C" int rt_camera_set_option(rt_camera* c, int32_t key, int32_t value) {
@@ -2543,9 +1914,9 @@ extern "C" int rt_camera_get_option(const rt_camera* c, int32_t key, int32_t* va
     case kOptFlat: *value = c->flat_variant; return RT_OK;
     case kOptRaysUsed: *value = c->last_rays; return RT_OK;
     case kOptDebug: *value = c->debug; return RT_OK;
-    case kOptSplitUsed: *value = c->order_split; return RT_OK;
+    case kOptSplitUsed: *value = c->order.split(); return RT_OK;
     case kOptFastUsed: *value = c->last_fast; return RT_OK;
-    case kOptOrderRestores: *value = (int32_t)std::min<uint64_t>(c->restores, INT32_MAX); return RT_OK;
+    case kOptOrderRestores: *value = (int32_t)std::min<uint64_t>(c->order.restores(), INT32_MAX); return RT_OK;
     case kOptFineTiles: *value = (int32_t)std::min<int64_t>(c->last_fine, INT32_MAX); return RT_OK;
     case kOptShadowOrder: *value = c->shadow_order >= 0 ? c->shadow_order : c->any_best; return RT_OK;
     case 10:
@@ -2646,13 +2017,13 @@ static int run_frames_multiframe(rt_camera* c, const rt_frame_loop* a, int32_t n
     // wave this call's launches take (the multi-frame rule of auto_rays, or
     // RT_OPT_RAYS), from the frame's geometry (static within the call)
     bool split_ok = false;
-    if (RT_MF_SPLIT && a->mode == RT_MODE_KD && effective_kernel(c) == 3 && c->obj) {
+    if (RT_MF_SPLIT && a->mode == RT_MODE_KD && c->kernel_version == 3 && c->obj) {
         TraceParams tp{};
         split_ok = frame_geometry(camera_geom(c), a->xform, tile, a->mode, tp) && tp.rays != 32;
     }
     const auto h0 = std::chrono::steady_clock::now();
     for (int32_t j = 0; j < nframes && !rc;) {
-        const bool have_order = c->tile_order < 3 || c->order_gen == c->layout_gen;
+        const bool have_order = c->tile_order < 3 || c->order.has_cost_order();
         const int32_t chunk = have_order ? std::min(nframes - j, kPersistChunk) : 1;
         const bool time_it = every > 0;
         const int pair = (int)(nbracket % kRing);

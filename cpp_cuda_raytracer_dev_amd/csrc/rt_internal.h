@@ -1,4 +1,4 @@
-// rt_internal.h -- shared between the host C++ (scene_host.cpp, rt_api.cpp)
+// rt_internal.h -- shared between the host C++ (scene_host.cpp, rt_api.cpp, tile_order.cpp)
 // and the HIP kernels (rt_kernels.hip).  Device-side data layouts live here.
 #pragma once
 
@@ -8,6 +8,7 @@
 #include <vector>
 
 #include "../../include/rt_mi355x.h"
+#include "rt_tile_consts.h"
 
 namespace rt {
 
@@ -24,10 +25,7 @@ constexpr uint32_t kLeafBit = 0x80000000u;
 // the maximum DFS occupancy of its balanced median tree; 24 covers 2^23 tris.
 constexpr int kMaxDepth = 24;
 
-// Per-pixel kernels: a block is a tile_w x 8 pixel tile made of 8x8-pixel
-// wave64s (tile_w = 32 for the flat kernel, 16 for the KD kernel, whose LDS
-// stack is three words per entry).
-constexpr int kTileH = 8;
+// Tile widths (kTileH and the tile shapes' comment: rt_tile_consts.h)
 constexpr int kTileWFlat = 32;
 constexpr int kTileWKd = 16;
 constexpr int kBlockMax = 256;
@@ -57,7 +55,7 @@ enum Option : int32_t {
     kOptSplitUsed = 9,  // get only: split tiles at the head of the current cost order (kernel 3)
     // 10, 11: retired (ABI 2; round 4's coop-used and frame-group keys)
     kOptFastUsed = 12,  // get only: which walks of the last kernel-3 render took the kFast forms (bit mask)
-    kOptOrderRestores = 13,  // get only: kept cost orders restored (restore_order)
+    kOptOrderRestores = 13,  // get only: kept cost orders restored (TileOrder::restore_order)
     kOptFineTiles = 14,  // get only: fine tiles (one kRays unit per wave) of the last kernel-3 render
     kOptDebug = 100,    // diagnostics: 1 = skip traversal, 2 = per-wave timestamps, 4 = every group
                         // coarse, 8 = coarse kernel on a side stream beside the fine one,
@@ -70,20 +68,6 @@ enum Option : int32_t {
     kOptPoolCap = 101,  // tests: shrink kernel 3's item pool (66..kPoolCap) to force its fallback
 };
 constexpr int kPoolCapMax = 640;
-
-// Waves per block of the wave-cooperative kernel: a block is one fine tile,
-// each wave one kRays-pixel unit of it.  16- and 8-ray units may run
-// RT_KD3_WAVES per block (2 or 4; the tile's waves share the CU's L1), 32-
-// and 64-ray units run 2.  The per-unit cost slots hold up to 4 waves.
-#ifndef RT_KD3_WAVES
-#define RT_KD3_WAVES 4
-#endif
-__host__ __device__ constexpr int kd3_waves(int rays) { return rays <= 16 ? RT_KD3_WAVES : 2; }
-// Kernel 3's per-tile cost slots (pool iterations): slots 0-3 the waves of a
-// tile, 4-7 the second half's waves of a split tile (zero otherwise), so a
-// split tile's cost is the max over both halves, not whichever half wrote
-// last (that race reordered the heavy tiles at random between samples).
-constexpr int kCostSlots = 8;
 
 // ---------------------------------------------------------------------------
 // Device layouts (all 16-byte aligned, read with dwordx4 loads).

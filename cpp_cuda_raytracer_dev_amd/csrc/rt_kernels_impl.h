@@ -171,7 +171,7 @@ __device__ __forceinline__ bool over_keeps(const TraceParams& P, bool hit, float
 // host's permutation by the tiles' measured cost in an earlier frame,
 // heaviest first (centre-out until costs arrive); order 4: the same per XCD
 // over 8 screen regions of equal cost; order 5: per XCD over 8 row bands of
-// equal tile count (rt_api.cpp cost_order).
+// equal tile count (tile_order_host.h cost_order).
 __device__ __forceinline__ int32_t tile_index(const TraceParams& P, int32_t b) {
     const int32_t nblocks = P.tiles_x * P.block_rows;
     if (P.tile_order == 0) {
