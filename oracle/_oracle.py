@@ -44,7 +44,12 @@ _lib = None
 
 
 def build() -> str:
+    """liboracle.so, and the reference's own sources compiled for the CPU
+    (oracle/ref_build.py: oracle/_ref/libref.so, which pins this restatement;
+    a no-op where the reference tree is absent)."""
     subprocess.run(["make", "-s", "-C", _HERE], check=True)
+    from . import ref_build
+    ref_build.build()
     return _LIB_PATH
 
 
@@ -76,6 +81,11 @@ def lib():
         L.orc_phong.argtypes = [P, P, P, P]
         L.orc_phong.restype = C.c_uint32
         L.orc_window_frame.argtypes = [P, P, P, C.c_int64, P]
+        L.orc_render_planes.argtypes = [P, P, C.c_int, P, P, P, P, C.c_int]
+        L.orc_host_vector_norm_n.argtypes = [P, C.c_int64, P]
+        L.orc_host_vector_norm_n.restype = None
+        L.orc_device_inverse_sqrt_n.argtypes = [P, C.c_int64, P]
+        L.orc_device_inverse_sqrt_n.restype = None
         _lib = L
     return _lib
 
@@ -167,6 +177,23 @@ class Scene:
         if rc != 0:
             raise RuntimeError(f"orc_render failed: {rc}")
         return argb, hit, cnt
+
+    def render_planes(self, mode=0, xform=None, nthreads=0):
+        """-> (argb [n], hit [n], aov [10, n] f32, cxx_defined [n] bool): the frame
+        with the planes of Camera::pixel_memory as a first frame leaves them
+        (orc_render_planes); cxx_defined is False where a pixel's (u8)(float)
+        has no value in C++ and only CUDA's conversion defines its colour."""
+        n = self.cam.w * self.cam.h
+        argb = np.zeros(n, np.uint32)
+        hit = np.full(n, -1, np.int64)
+        aov = np.zeros((10, n), np.float32)
+        ok = np.zeros(n, np.uint8)
+        X = None if xform is None else np.ascontiguousarray(xform, np.float32)
+        rc = lib().orc_render_planes(self._h, None if X is None else _ptr(X), mode, _ptr(argb), _ptr(hit), _ptr(aov),
+                                     _ptr(ok), nthreads)
+        if rc != 0:
+            raise RuntimeError(f"orc_render_planes failed: {rc}")
+        return argb, hit, aov, ok.astype(bool)
 
     def close(self):
         if self._h:

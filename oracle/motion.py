@@ -88,8 +88,13 @@ class V4:
 class Motion:
     """One Object's transform state after Camera::add_object (TD/Camera.cpp:131-134)."""
 
-    def __init__(self, cam_pos, cam_n, cam_u, speed=F(.005)):
+    def __init__(self, cam_pos, cam_n, cam_u, speed=F(.005), contract=True):
+        """contract=False: the device translation column without nvcc's fma
+        (_device_translate), the reference's source as written; what its
+        sources give when compiled with -ffp-contract=off
+        (tests/test_ref_cpu.py).  Nothing else depends on it."""
         p = [F(v) for v in cam_pos]
+        self.contract = bool(contract)
         self.n = [F(v) for v in cam_n]
         self.u = [F(v) for v in cam_u]
         self.speed = F(speed)
@@ -129,10 +134,11 @@ class Motion:
         v.x, v.y, v.z = out
 
     def _device_translate(self, t: V4, scale: int):
-        """update_voxel_transform_m_translate_cuda (TD/Camera.cu:188-192), contracted."""
+        """update_voxel_transform_m_translate_cuda (TD/Camera.cu:188-192),
+        contracted unless contract=False."""
         s = F(scale)
         for r, c in zip(self.drot, (t.x, t.y, t.z)):
-            r.w = fma32(F(s * c), t.w, r.w)
+            r.w = fma32(F(s * c), t.w, r.w) if self.contract else F(r.w + F(F(s * c) * t.w))
 
     def transform(self, t_vec, select: int):
         """transform_camera_voxel_device_memory (TD/Camera.cu:254-335)."""

@@ -55,6 +55,13 @@ float orc_device_inverse_sqrt(float x, float y, float z) {
     return u.f;
 }
 
+void orc_host_vector_norm_n(const float* s, int64_t n, float* out) {
+    for (int64_t i = 0; i < n; i++) out[i] = orc_host_vector_norm(s[i]);
+}
+void orc_device_inverse_sqrt_n(const float* xyz, int64_t n, float* out) {
+    for (int64_t i = 0; i < n; i++) out[i] = orc_device_inverse_sqrt(xyz[3 * i], xyz[3 * i + 1], xyz[3 * i + 2]);
+}
+
 /* device_normalize_vector, TD/vector.cuh:116-120 */
 static void dev_normalize(float* x, float* y, float* z) {
     float r = orc_device_inverse_sqrt(*x, *y, *z);
@@ -583,8 +590,9 @@ void orc_scene_destroy(orc_scene* s) {
 
 /* --------------------------------------------------------------- shading */
 
-uint32_t orc_phong(const float pnt[3], const float nrm[3], const float rmd[3],
-                   const float rad[3]) {
+/* The three floats color_cam_cuda converts to u8 (TD/Camera.cu:57-59). */
+static void phong_ratios(const float pnt[3], const float nrm[3], const float rmd[3],
+                         const float rad[3], float t[3]) {
     /* color_cam_cuda, TD/Camera.cu:27-60 */
     float sdx = 2 - pnt[0], sdy = 2 - pnt[1], sdz = 2 - pnt[2];
     dev_normalize(&sdx, &sdy, &sdz);
@@ -599,10 +607,28 @@ uint32_t orc_phong(const float pnt[3], const float nrm[3], const float rmd[3],
     pg += (rad[1] * diff) + (1 * spec);
     pb += (rad[2] * diff) + (1 * spec);
     float mx = fmaxf(fmaxf(pr, pg), pb);
-    uint32_t r8 = to_u8((pr / mx) * 255);
-    uint32_t g8 = to_u8((pg / mx) * 255);
-    uint32_t b8 = to_u8((pb / mx) * 255);
+    t[0] = (pr / mx) * 255;
+    t[1] = (pg / mx) * 255;
+    t[2] = (pb / mx) * 255;
+}
+
+uint32_t orc_phong(const float pnt[3], const float nrm[3], const float rmd[3],
+                   const float rad[3]) {
+    float t[3];
+    phong_ratios(pnt, nrm, rmd, rad, t);
+    uint32_t r8 = to_u8(t[0]);
+    uint32_t g8 = to_u8(t[1]);
+    uint32_t b8 = to_u8(t[2]);
     return (r8 << 16) | (g8 << 8) | b8;
+}
+
+/* Whether (u8)t of TD/Camera.cu:57-59 has a value in C++ for each channel
+ * ([conv.fpint]: the truncated value fits the type).  Where it has none only
+ * CUDA's saturating cvt defines the pixel (H14, to_u8 above). */
+static int phong_defined(const float t[3]) {
+    for (int k = 0; k < 3; k++)
+        if (!(t[k] > -1.0f && t[k] < 256.0f)) return 0;
+    return 1;
 }
 
 /* ------------------------------------------------------------- intersect */
@@ -848,9 +874,24 @@ int orc_render(const orc_scene* s, const float xform[12], int mode, int32_t row0
     return orc_render_ex(s, xform, mode, 0, row0, row1, argb, hit, counters, nthreads);
 }
 
+static int render_impl(const orc_scene* s, const float xform[12], int mode, int flags, int32_t row0,
+                       int32_t row1, uint32_t* argb, int64_t* hit, uint64_t counters[ORC_CNT_N],
+                       int nthreads, float* aov, uint8_t* cxx_defined);
+
 int orc_render_ex(const orc_scene* s, const float xform[12], int mode, int flags, int32_t row0,
                   int32_t row1, uint32_t* argb, int64_t* hit, uint64_t counters[ORC_CNT_N],
                   int nthreads) {
+    return render_impl(s, xform, mode, flags, row0, row1, argb, hit, counters, nthreads, NULL, NULL);
+}
+
+int orc_render_planes(const orc_scene* s, const float xform[12], int mode, uint32_t* argb,
+                      int64_t* hit, float* aov, uint8_t* cxx_defined, int nthreads) {
+    return render_impl(s, xform, mode, 0, 0, s->cam.h, argb, hit, NULL, nthreads, aov, cxx_defined);
+}
+
+static int render_impl(const orc_scene* s, const float xform[12], int mode, int flags, int32_t row0,
+                       int32_t row1, uint32_t* argb, int64_t* hit, uint64_t counters[ORC_CNT_N],
+                       int nthreads, float* aov, uint8_t* cxx_defined) {
     static const float ident[12] = {1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1, 0};
     const float* X = xform ? xform : ident;
     const int32_t w = s->cam.w;
@@ -896,6 +937,25 @@ int orc_render_ex(const orc_scene* s, const float xform[12], int mode, int flags
                 }
                 if (argb) argb[i] = c;
                 if (hit) hit[i] = h.rmi;
+                if (aov) {
+                    /* Camera::pixel_memory after the first frame: d_dist = 400, the
+                     * rest zero (init_cam_mem_cuda, TD/Camera.cu:97-110) unless hit */
+                    const int64_t np_ = (int64_t)w * s->cam.h;
+                    float v[10] = {ORC_DRAW_DISTANCE, 0, 0, 0, 0, 0, 0, 0, 0, 0};
+                    if (h.rmi >= 0) {
+                        v[0] = h.d;
+                        for (int k = 0; k < 3; k++) { v[1 + k] = h.pnt[k]; v[4 + k] = h.nrm[k]; v[7 + k] = h.rad[k]; }
+                    }
+                    for (int k = 0; k < 10; k++) aov[k * np_ + i] = v[k];
+                }
+                if (cxx_defined) {
+                    cxx_defined[i] = 1;
+                    if (h.rmi >= 0) {
+                        float t[3];
+                        phong_ratios(h.pnt, h.nrm, rmd, h.rad, t);
+                        cxx_defined[i] = (uint8_t)phong_defined(t);
+                    }
+                }
             }
         }
 #ifdef _OPENMP

@@ -5,13 +5,17 @@
  * import or call this library: it is the parity checker used by tests/,
  * __graft_entry__.smoke() and bench.py's cpu_baseline leg.
  *
- * Parity status: "parity unpinned" against the reference binary -- the
- * reference (ams3878/cpp_cuda_raytracer_dev) ships no tests, no golden
- * vectors, and compiling/running it in this environment was denied (SURVEY.md
- * §8c).  This restatement is pinned instead against (1) an independent numpy
- * restatement (oracle/np_oracle.py) on small scenes, (2) hand-derived
- * known-answer tests (tests/test_oracle_kat.py) and (3) structural invariants
- * of the KD tree.  See DESIGN.md §Parity.
+ * Parity status: pinned to the reference's source semantics without
+ * contraction.  The reference (ams3878/cpp_cuda_raytracer_dev) ships no tests
+ * and no golden vectors and its CUDA binary cannot be built here, but its
+ * sources compile for the CPU (oracle/ref_build.py -> oracle/_ref/libref.so)
+ * and tests/test_ref_cpu.py compares this restatement with them bit for bit:
+ * PLY input, sort, KD build, camera, both intersect kernels, Phong, the
+ * window buffer.  Not pinned: ptxas' contraction choices, CUDA's powf, the
+ * shadow walk and the visit counters (the reference has neither).  Further
+ * anchors: an independent numpy restatement (oracle/np_oracle.py), hand-derived
+ * known-answer tests and structural invariants of the KD tree.  See
+ * DESIGN.md §Parity.
  *
  * Every function cites the reference file:line it restates
  * (TD/ = TEST_Dungeonrun/ in the reference tree).
@@ -123,6 +127,19 @@ int orc_render(const orc_scene* s, const float xform[12], int mode,
 int orc_render_ex(const orc_scene* s, const float xform[12], int mode, int flags,
                   int32_t row0, int32_t row1, uint32_t* argb, int64_t* hit,
                   uint64_t counters[ORC_CNT_N], int nthreads);
+
+/* One whole KD or flat frame with the ten planes of Camera::pixel_memory
+ * (TD/Camera.h:50-59) as they stand after a first frame: aov[k * w * h + i],
+ * k = d, pnt.xyz, norm.xyz, rad.rgb; a miss keeps d = 400 and zeros
+ * (init_cam_mem_cuda, TD/Camera.cu:97-110).  cxx_defined[i] (may be NULL) is 0
+ * where a (u8)(float) of TD/Camera.cu:57-59 has no value in C++ (NaN, <= -1
+ * or >= 256): there only CUDA's saturating conversion defines the colour. */
+int orc_render_planes(const orc_scene* s, const float xform[12], int mode, uint32_t* argb,
+                      int64_t* hit, float* aov, uint8_t* cxx_defined, int nthreads);
+
+/* The inverse square roots over arrays (s[n]; xyz[3 n]). */
+void orc_host_vector_norm_n(const float* s, int64_t n, float* out);
+void orc_device_inverse_sqrt_n(const float* xyz, int64_t n, float* out);
 
 /* One primary ray (init_cam_mem_cuda, TD/Camera.cu:103-104). */
 void orc_primary_ray(const orc_camera* cam, int32_t ix, int32_t iy, float out[3]);

@@ -160,3 +160,51 @@ def mesh_matches(ent) -> bool:
     if ent["scene"] not in _mesh_sha:
         _mesh_sha[ent["scene"]] = scenes.mesh_sha(ent["scene"])
     return _mesh_sha[ent["scene"]] == ent["mesh_sha"]
+
+
+# ------------------------------------------------- generators shared by CPU and GPU modules
+
+def random_leafs(n, seed, ties, zeros=False):
+    """Seeded leaf boxes for the KD builders: integer-valued boxes that tie
+    (ties), +-0 bounds (zeros), a random triangle numbering."""
+    rng = np.random.default_rng(seed)
+    if ties:
+        lo = rng.integers(-4, 4, size=(n, 3)).astype(np.float32)
+        hi = lo + rng.integers(0, 3, size=(n, 3)).astype(np.float32)
+    else:
+        lo = rng.random((n, 3)).astype(np.float32) - 0.5
+        hi = lo + rng.random((n, 3)).astype(np.float32)
+    if zeros:  # -0.0 and +0.0 compare equal in the reference's sort (`<`)
+        z = rng.random((n, 3)) < 0.3
+        lo[z] = np.where(rng.random(z.sum()) < 0.5, np.float32(-0.0), np.float32(0.0))
+        hi = np.maximum(hi, lo)
+        hi[rng.random((n, 3)) < 0.1] = np.float32(-0.0)
+        lo = np.minimum(lo, hi)
+    pl = np.zeros(n, _leaf_aabb_dtype())
+    for i, f in enumerate(("x", "y", "z")):
+        pl[f + "0"] = lo[:, i]
+        pl[f + "1"] = hi[:, i]
+    pl["tri"] = rng.permutation(n)
+    return pl
+
+
+def _leaf_aabb_dtype():
+    from cpp_cuda_raytracer_dev_amd import _lib
+    return _lib.LEAF_AABB_DTYPE
+
+
+def poses(n, seed=7):
+    """n seeded camera poses around the rabbit, looking at its middle."""
+    rng = np.random.default_rng(seed)
+    out = []
+    for _ in range(n):
+        d = rng.normal(size=3)
+        d /= np.linalg.norm(d)
+        pos = (np.array([-0.02, 0.11, 0.0]) + (0.35 + 0.4 * rng.random()) * d).astype(np.float32)
+        out.append(dict(pos=tuple(float(x) for x in pos), look_at=(-0.02, 0.11, 0.0)))
+    return out
+
+
+#: object transforms of the fast-walk tests: rotations about y with offsets up to 0.3
+FAST_XFORMS = [rot_y(17.0), rot_y(0.0, (0.01, -0.005, 0.02)), rot_y(-9.0, (0.0, 0.01, 0.0)),
+               rot_y(31.0, (0.05, 0.02, 0.3)), rot_y(-52.0, (-0.03, 0.0, -0.2))]

@@ -28,26 +28,7 @@ def test_gpu_build_equals_host_build(name):
     _same_nodes(R.kd_build_gpu(leafs), H.product_tree(name), name)
 
 
-def _random_leafs(n, seed, ties, zeros=False):
-    rng = np.random.default_rng(seed)
-    if ties:
-        lo = rng.integers(-4, 4, size=(n, 3)).astype(np.float32)
-        hi = lo + rng.integers(0, 3, size=(n, 3)).astype(np.float32)
-    else:
-        lo = rng.random((n, 3)).astype(np.float32) - 0.5
-        hi = lo + rng.random((n, 3)).astype(np.float32)
-    if zeros:  # -0.0 and +0.0 compare equal in the reference's sort (`<`)
-        z = rng.random((n, 3)) < 0.3
-        lo[z] = np.where(rng.random(z.sum()) < 0.5, np.float32(-0.0), np.float32(0.0))
-        hi = np.maximum(hi, lo)
-        hi[rng.random((n, 3)) < 0.1] = np.float32(-0.0)
-        lo = np.minimum(lo, hi)
-    pl = np.zeros(n, _lib.LEAF_AABB_DTYPE)
-    for i, f in enumerate(("x", "y", "z")):
-        pl[f + "0"] = lo[:, i]
-        pl[f + "1"] = hi[:, i]
-    pl["tri"] = rng.permutation(n)
-    return pl
+_random_leafs = H.random_leafs  # (shared with tests/test_ref_cpu.py)
 
 
 @pytest.mark.parametrize("n,seed,ties,zeros", [(1, 0, False, False), (2, 1, False, False), (3, 2, True, False),

@@ -417,15 +417,7 @@ def test_object_transform(xf, kernel):
     _assert_same((argb, hit), (oargb, ohit), "xform")
 
 
-def _poses(n, seed=7):
-    rng = np.random.default_rng(seed)
-    out = []
-    for _ in range(n):
-        d = rng.normal(size=3)
-        d /= np.linalg.norm(d)
-        pos = (np.array([-0.02, 0.11, 0.0]) + (0.35 + 0.4 * rng.random()) * d).astype(np.float32)
-        out.append(dict(pos=tuple(float(x) for x in pos), look_at=(-0.02, 0.11, 0.0)))
-    return out
+_poses = H.poses  # (shared with tests/test_ref_cpu.py)
 
 
 @pytest.mark.parametrize("pose", _poses(6))
@@ -1675,8 +1667,7 @@ def test_fast_walk_same_frame(scene, w, h, pose, shadow):
 # TD/WinMain.cpp:186-209 -> TD/Camera.cu:254-335): a rotation keeps the
 # untranslated walk (kFast slots under the rotated proof), an offset takes
 # the translated walk's xfast_slot; both must equal the double forms.
-FAST_XFORMS = [_rot_y(17.0), _rot_y(0.0, (0.01, -0.005, 0.02)), _rot_y(-9.0, (0.0, 0.01, 0.0)),
-               _rot_y(31.0, (0.05, 0.02, 0.3)), _rot_y(-52.0, (-0.03, 0.0, -0.2))]
+FAST_XFORMS = H.FAST_XFORMS  # (shared with tests/test_ref_cpu.py)
 
 
 @pytest.mark.parametrize("shadow", [False, True])
