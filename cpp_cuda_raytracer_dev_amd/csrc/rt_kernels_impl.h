@@ -1023,7 +1023,7 @@ __device__ __forceinline__ float opaque(float x) {
 // component itself (r_a * 1 + r_b * 0 + r_c * 0 == r_a for finite nonzero r),
 // and the entry test mint1 >= maxt0 - 1e-16 && maxt0 > -1e-16
 // (TD/Trixel.cu:146) is mint1 >= maxt0: P.fast holds only when every box's
-// maxt0 is >= 2^-20 for every ray of the frame (rt_api.cpp fast_proof), where
+// maxt0 is >= 2^-20 for every ray of the frame (frame_geom.cpp fast_proof), where
 // maxt0 - 1e-16 rounds to a double above the float below maxt0.)
 template <bool kTranslated, bool kCount, bool kAny>
 __device__ __forceinline__ void order_node(const TraceParams& P, float4 q2, float4 q3, float4 q4, float t0, float t1,
@@ -1292,7 +1292,7 @@ __device__ __forceinline__ int fast_slot(const TraceParams& P, uint4* items, int
 // 2-3): the walks of an object moved by an offset (its rays carry the
 // translation od, TD/Trixel.cu:60-66,94-95) and the shadow walks from the
 // light (od = (-2, -2, -2), a12), under a proof that every box's entry
-// parameter is >= 2^-20 for each of their rays (rt_api.cpp fast_proof for the
+// parameter is >= 2^-20 for each of their rays (frame_geom.cpp fast_proof for the
 // frame; fast_proof_shadow for the light plus trace_unit's per-wave sign
 // check).  The reference's tests, exactly, in single precision:
 //   * entry (TD/Trixel.cu:146): mint1 >= maxt0 (maxt0 >= 2^-20, as kFast);
@@ -1736,7 +1736,7 @@ __device__ __forceinline__ int two_level_fast(const TraceParams& P, uint4* items
 //   kWalkXFast  (round 6) a translated nearest-hit walk or a shadow walk
 //               whose proof holds (xfast_slot; nearest-hit two-level
 //               iterations two_level_fast<kXl>).
-// The last two are the "kFast walks" of the comments here and in rt_api.cpp.
+// The last two are the "kFast walks" of the comments here and in frame_geom.cpp.
 enum WalkForm { kWalkRef, kWalkFast, kWalkXFast };
 template <int kCap, int kStride, bool kTranslated, bool kCount, bool kAny, int kOrder = 0, WalkForm kForm = kWalkRef,
           int kOct = 8, bool kOdP = false>
@@ -1959,9 +1959,9 @@ __device__ __forceinline__ void trace_unit(const TraceParams& P, WaveLds<kRays, 
         float rn0 = 1.0f;
         camera_ray<false, !kTranslated>(P, px, live, cam0, R0, rn0);
         // every live ray's components normal and nonzero (1/r finite), under
-        // the frame proof P.fast (rt_api.cpp)
+        // the frame proof P.fast (frame_geom.cpp)
         // (translated walks: the xfast_slot forms under the same proof,
-        // whose margins cover the offsets, rt_api.cpp fast_proof)
+        // whose margins cover the offsets, frame_geom.cpp fast_proof)
         fast = P.fast && __ballot(live && !(fabsf(R0.rx) >= 0x1p-126f && fabsf(R0.ry) >= 0x1p-126f &&
                                             fabsf(R0.rz) >= 0x1p-126f)) == 0ull;
         if (fast) {  // (the octant of the object-space rays)
@@ -2074,7 +2074,7 @@ __device__ __forceinline__ void trace_unit(const TraceParams& P, WaveLds<kRays, 
         }
         __builtin_amdgcn_wave_barrier();
         // the translated kFast slots when the light's proof holds
-        // (rt_api.cpp fast_proof_shadow: the root box beyond the light's
+        // (frame_geom.cpp fast_proof_shadow: the root box beyond the light's
         // plane on axis P.sh_axis) and every live shadow ray points into that
         // side with normal, nonzero components: then every box's entry
         // parameter is >= 2^-20 for it
@@ -2320,7 +2320,7 @@ __device__ __forceinline__ bool ray_has_tiny_component(const TraceParams& P, int
 template <bool kWriteHit, bool kCount>
 __device__ __forceinline__ bool fill_far(const TraceParams& P, const Unit& G, int lane, Counts& C) {
     // P.far_all: the host proved the box behind the eye for every pixel
-    // (rt_api.cpp box_behind, any transform, zero components included)
+    // (frame_geom.cpp box_behind, any transform, zero components included)
     if (!P.far_all && !far_group(P, G)) return false;
     Pixel px;
     const bool live = unit_pixel(P, G, 8, lane, px);
@@ -2885,7 +2885,7 @@ __device__ __forceinline__ float floor_f(double d) {
 // flags |= kCamTinyS1 when some node's s1 is tiny, kCamUnordered when some
 // child box has a low bound not <= its high bound or is not inside its
 // parent's box (the kFast walk needs ordered boxes, and its frame proof
-// boxes inside the root's: rt_api.cpp fast_proof).
+// boxes inside the root's: frame_geom.cpp fast_proof).
 __global__ void k_cam_nodes(const rt_kd_node* __restrict__ nodes, const int32_t* __restrict__ ids,
                             const uint32_t* __restrict__ node_ref, int64_t ninterior, float cx,
                             float cy, float cz, float4* __restrict__ out, int32_t* __restrict__ flags,

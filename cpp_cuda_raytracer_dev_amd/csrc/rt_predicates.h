@@ -16,7 +16,7 @@
 // -DRT_FAST_PREDICATES: on gfx950 their branches cost more than the double
 // arithmetic they skip (0.126 vs 0.118 ms per 1080p dragon frame, round 1).
 // The default kernels instead take branch-free float forms wherever a frame
-// PROVES that no operand is tiny (rt_kernels_impl.h kFast walks, rt_api.cpp
+// PROVES that no operand is tiny (rt_kernels_impl.h kFast walks, frame_geom.cpp
 // fast_proof: every box's maxt0 >= 2^-20, so the entry test is the float
 // mint1 >= maxt0, and the ordering compares use the exact float thresholds
 // k_cam_nodes stores), and the double forms below (the *_ref functions)

@@ -1,7 +1,10 @@
-// rt_tile_consts.h -- the tile constants shared by the kernels (through
-// rt_internal.h) and the tile-order arithmetic (tile_order_host.h).  No HIP
-// include: tests/tile_order_main.cpp compiles it with a plain C++ compiler.
+// rt_tile_consts.h -- the constants shared by the kernels (through
+// rt_internal.h), the tile-order arithmetic (tile_order_host.h) and the
+// launch geometry (frame_geom.cpp).  No HIP include: tests/tile_order_main.cpp
+// and tests/frame_geom_main.cpp compile it with a plain C++ compiler.
 #pragma once
+
+#include <stdint.h>
 
 namespace rt {
 
@@ -9,6 +12,12 @@ namespace rt {
 // wave64s (tile_w = 32 for the flat kernel, 16 for the KD kernel, whose LDS
 // stack is three words per entry).
 constexpr int kTileH = 8;
+constexpr int kTileWFlat = 32;
+constexpr int kTileWKd = 16;
+constexpr int kBlockMax = 256;
+
+// k_cam_nodes' flags of a camera's records
+constexpr int32_t kCamTinyS1 = 1, kCamUnordered = 2, kCamSplitFields = 4;
 
 // Waves per block of the wave-cooperative kernel: a block is one fine tile,
 // each wave one kRays-pixel unit of it.  16- and 8-ray units may run

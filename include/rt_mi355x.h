@@ -15,6 +15,7 @@
 #ifndef RT_MI355X_H
 #define RT_MI355X_H
 
+#include <stddef.h>
 #include <stdint.h>
 
 #ifdef __cplusplus

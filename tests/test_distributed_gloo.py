@@ -144,7 +144,7 @@ def test_rect_gather_protocol_disagreement_raises():
 
 
 def test_frame_rect_box_behind_eye_is_empty():
-    """The box-behind-the-eye proof (rt_api.cpp box_behind, VERDICT r03 item
+    """The box-behind-the-eye proof (frame_geom.cpp box_behind, VERDICT r03 item
     5) from host-side inputs: the poses of bench.py --animate R+W.Q.T.W after
     the object has passed the camera give an empty gather rectangle (every
     pixel background, nothing sent) -- and the oracle renders those poses as

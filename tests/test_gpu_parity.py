@@ -1409,7 +1409,7 @@ def test_shim_ranks_gather_c5():
 def test_far_along_key_sequence_background():
     """bench.py --animate R+W.Q.T.W carries the object past
     the camera after ~500 ticks (the oracle shows background only).  The host
-    then proves the box behind the eye for every pixel (rt_api.cpp
+    then proves the box behind the eye for every pixel (frame_geom.cpp
     box_behind): no fine tiles, every group filled as background by the fine
     kernel's blocks (far_all), and the N > 1 gather rectangle is empty.  The
     frames equal the oracle's at those poses (and at poses where the object is
@@ -1609,7 +1609,7 @@ def test_multiframe_alternating_loops_kept_order():
 
 # kFast walks (rt_kernels_impl.h fast_slot / order_node<kFast>): the float
 # entry test and the float ordering thresholds must give the reference's
-# frame, its visit counts included, wherever rt_api.cpp fast_proof admits
+# frame, its visit counts included, wherever frame_geom.cpp fast_proof admits
 # the frame.  Each pose renders with the proof's walks and with debug bit
 # 2048 (the double-promoted forms) and the two must agree bit for bit; the
 # default view is also checked against the oracle.
