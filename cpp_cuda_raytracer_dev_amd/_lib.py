@@ -117,6 +117,7 @@ SIGNATURES = {
     "rt_render_into": (C.c_int, [_P, _P, C.c_uint32, C.c_uint32, C.POINTER(RtTile), _P, _P, _P]),
     "rt_render_display": (C.c_int, [_P, _P, C.c_uint32, C.c_uint32, C.POINTER(RtTile), _P, _P, _P, _P]),
     "rt_render_over": (C.c_int, [_P, _P, C.c_uint32, C.c_uint32, C.POINTER(RtTile), _P, _P, C.c_int64, _P]),
+    "rt_shadow_over": (C.c_int, [_P, _P, C.c_uint32, C.POINTER(RtTile), _P, _P, C.c_int64, C.c_int32, _P]),
     "rt_render_clear": (C.c_int, [_P, C.c_uint32, C.POINTER(RtTile), _P, _P, _P]),
     "rt_camera_targets": (C.c_int, [_P, C.POINTER(_P), C.POINTER(_P), C.POINTER(_P), C.POINTER(C.c_int64)]),
     "rt_tile_packed_pixels": (C.c_int64, [C.c_int32, C.c_int32, C.c_int32]),

@@ -1000,6 +1000,105 @@ extern "C" int rt_render_clear(rt_camera* c, uint32_t flags, const rt_tile* tile
     return launch_clear(c->w, c->h, nr, rk, frame_out, d_argb, d_hit, aov, stride, stream);
 }
 
+// The deferred shadow pass (k_shadow_kd3).  Its launch parameters are built
+// here from the camera alone, beside the renders' machinery rather than
+// through it: the pass has no fine region, cost order, held region or cached
+// geometry, and must leave the camera's (fill_params' caches, TileOrder) as
+// the renders left them.
+extern "C" int rt_shadow_over(rt_camera* c, const float* xform, uint32_t flags, const rt_tile* tile, uint32_t* d_argb,
+                              int64_t* d_hit, int64_t hit_base, int32_t skip_own, void* stream) {
+    if (!c) return fail(RT_ERR_INVALID, "rt_shadow_over: null camera");
+    if (flags & ~(RT_FLAG_COUNT | RT_FLAG_FRAME_OUT))
+        return fail(RT_ERR_INVALID, "rt_shadow_over: flags 0x%x (RT_FLAG_COUNT and RT_FLAG_FRAME_OUT are accepted)", flags);
+    if (hit_base < 0) return fail(RT_ERR_INVALID, "rt_shadow_over: hit_base %lld", (long long)hit_base);
+    int rc = check_tile(tile);
+    if (rc) return rc;
+    if (d_argb && !d_hit) return fail(RT_ERR_INVALID, "rt_shadow_over: a frame without its hit buffer (the owner is needed)");
+    if (!d_argb) {
+        d_argb = c->d_argb;
+        if (!d_hit) d_hit = c->d_hit;
+    }
+    if (c->kernel_version != 3)
+        return fail(RT_ERR_INVALID, "rt_shadow_over: shadow rays run in the wave-cooperative kernel (3); kernel %d",
+                    c->kernel_version);
+    if (!c->obj) return fail(RT_ERR_STATE, "camera has no object (rt_camera_add_object)");
+    if (!c->obj->d_nodes) return fail(RT_ERR_STATE, "rt_shadow_over: needs rt_scene_set_kd (Trixel::create_kd) first");
+    if (c->obj->ntri == 0) return fail(RT_ERR_STATE, "rt_shadow_over: empty scene");
+    const int32_t nr = tile ? tile->nranks : 1, rk = tile ? tile->rank : 0;
+    const bool frame_out = (flags & RT_FLAG_FRAME_OUT) != 0;
+    // plane 0 is read, never written: the bound planes (the caller's to fill,
+    // and to size) or the camera's own once something filled them
+    float* aov = c->aov_bound;
+    int64_t stride = c->aov_bound_stride;
+    if (aov) {
+        const int64_t need = nr > 1 && !frame_out ? rt_tile_packed_pixels(c->w, c->h, nr) : (int64_t)c->w * c->h;
+        if (stride < need)
+            return fail(RT_ERR_INVALID, "rt_shadow_over: plane stride %lld is below the %lld pixels this pass reads",
+                        (long long)stride, (long long)need);
+    } else {
+        if (!c->d_aov || !c->aov_filled)
+            return fail(RT_ERR_STATE, "rt_shadow_over: the camera's own planes hold no frame (render with "
+                                      "RT_FLAG_WRITE_AOV or rt_render_clear first)");
+        aov = c->d_aov;
+        stride = rt_tile_packed_pixels(c->w, c->h, 1);
+    }
+    DeviceGuard g(c->device);
+    if ((rc = prepare_camera_object(c))) return rc;
+    const rt_scene* s = c->obj;
+    TraceParams p{};
+    p.inode = c->d_inode;
+    p.trec = c->d_trec;
+    p.split_planes = (c->cam_flags & kCamSplitFields) ? c->d_split : nullptr;
+    p.leaf_off = c->leaf_off;
+    p.rec_bytes = c->leaf_off ? (uint32_t)(c->leaf_off + 64 * (uint64_t)s->ntri) : 0u;
+    p.shade = s->d_shade;
+    p.argb = d_argb;
+    p.hit = d_hit;
+    p.counters = c->d_counters;
+    p.err = c->d_err;
+    for (int k = 0; k < 3; k++) {
+        p.n_mod[k] = c->basis.n_mod[k];
+        p.u_mod[k] = c->basis.u_mod[k];
+        p.v_mod[k] = c->basis.v_mod[k];
+    }
+    memcpy(p.xf, xform ? xform : kIdentXf, sizeof p.xf);
+    p.w = c->w;
+    p.h = c->h;
+    p.nranks = nr;
+    p.rank = rk;
+    p.frame_out = frame_out ? 1 : 0;
+    // every tile of the rank's bands: 8 x 8 pixels, four 16-pixel units
+    p.rays = 16;
+    p.tile_w = 8;
+    p.tile_h = kd3_waves(16) * 2;
+    const int32_t nbands = (c->h + kTileH - 1) / kTileH;
+    p.tiles_x = (c->w + p.tile_w - 1) / p.tile_w;
+    p.block_rows = ((nbands + nr - 1) / nr) * (kTileH / p.tile_h);
+    // natural order unless the camera asks for XCD-contiguous runs (RT_OPT_TILE_ORDER 0):
+    // the grid is the whole frame and the work sits where the hits are, so a
+    // contiguous run per XCD leaves most XCDs idle (knot 1080p: 325 against 132 us)
+    p.tile_order = c->tile_order == 0 ? 0 : 1;
+    camera_relative_box(s->root, c->pos, p.root_box);
+    p.root_ref = s->root_ref;
+    p.ntri = s->ntri;
+    p.max_depth = kMaxDepth;
+    p.tree_height = s->height;
+    p.two_depth = -1;
+    p.tiny_s1 = (c->cam_flags & kCamTinyS1) ? 1 : 0;
+    p.plain_xf = 0;
+    p.fast = p.fast_sh = 0;  // the double forms (k_shadow_kd3's comment)
+    p.debug = c->debug;
+    p.pool_cap = c->pool_cap;
+    p.items = c->items;
+    // a fixed push order as given; timed (-1): the order in use, no timing frames here
+    p.any_order = (c->shadow_order >= 0 ? c->shadow_order : c->any_best) | ((c->debug & 16) ? 4 : 0);
+    p.aov = aov;
+    p.aov_stride = stride;
+    p.hit_base = hit_base;
+    p.shadow_skip_own = skip_own ? 1 : 0;
+    return launch_shadow_over(p, (flags & RT_FLAG_COUNT) != 0, stream);
+}
+
 extern "C" int rt_camera_targets(rt_camera* c, uint32_t** d_argb, int64_t** d_hit, float** d_aov, int64_t* plane_stride) {
     if (!c) return fail(RT_ERR_INVALID, "rt_camera_targets: null camera");
     const int64_t stride = rt_tile_packed_pixels(c->w, c->h, 1);

@@ -96,6 +96,9 @@ int launch_cam_nodes(const rt_kd_node* nodes, const int32_t* interior_ids,
 enum LaunchPart : int { kPartAll = 0, kPartFine = 1, kPartCoarse = 2 };
 int launch_trace(const TraceParams& p, uint32_t mode, uint32_t flags, int kernel_version,
                  void* stream, int part);
+// rt_shadow_over's pass (rt_shadow_dispatch.hip): k_shadow_kd3 over the
+// tiles_x * block_rows tiles of p, push order p.any_order.
+int launch_shadow_over(const TraceParams& p, bool count, void* stream);
 // Camera-relative box of one world node, exactly as init_cam_voxel_mem_cuda.
 void camera_relative_box(const rt_kd_node& nd, const float pos[3], float out[6]);
 // KD build on the GPU (kd_build_gpu.hip).  The median tree's shape depends

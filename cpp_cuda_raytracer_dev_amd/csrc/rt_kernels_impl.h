@@ -2494,6 +2494,86 @@ __global__ RT_KD3_BOUNDS(64 * kd3_waves(kRays)) void k_trace_kd3(TraceParams P) 
     kd3_block<kRays, kTranslated, kWriteHit, kCount, kShadow, kCap, kRayVec>(P, s_lds, b, wv, lane);
 }
 
+// rt_shadow_over: the deferred shadow pass of a composite.  The frame's hit
+// buffer and plane 0 hold, per pixel, the nearest hit's owner (hit_base +
+// triangle) and depth d, whichever object and kernel wrote them; this walks
+// the shadow segment of every hit pixel through THIS camera's tree, seeded
+// from the stored d instead of from a primary walk of the same object (the
+// expressions of trace_unit's kShadow block), and stores 0x00000000 where it
+// finds an occluder.  Nothing else is stored: not the frame elsewhere, not
+// the hit buffer, not the planes.  The pixel's own triangle is excluded only
+// where the pixel is this object's (hit_base <= hit < hit_base + ntri);
+// P.shadow_skip_own leaves those pixels out altogether (their render walked
+// them under RT_FLAG_SHADOW).
+// One 16-pixel unit (8 x 2) per wave over every tile of the rank's frame, in
+// natural or XCD-contiguous order (P.tile_order 1 / 0; the host sets no other):
+// a shadow volume is not confined to the object's screen rectangle, so there
+// is no fine region, no cost order and no split tile.  The walk takes the
+// reference's double forms (kWalkRef): the light's proof for the float forms
+// (frame_geom.cpp fast_proof_shadow) is argued for hit points inside this
+// object's root box, which another object's hit point need not be.
+// Any bit pattern in plane 0 terminates: the walk is a traversal of a finite
+// tree whose only float-dependent loop is rsqrt21's fixed 21 steps; a NaN d
+// makes Lmax NaN, root_pass's `t0 < lim` false, and the pool empty (a leaf
+// root's one test then fails `w < d` against the NaN Lmax).
+// kOrder: the any-hit push order (0..3), + 4: a counted walk stops at
+// occluders like a timed one (debug bit 16).
+template <bool kCount, int kOrder>
+__global__ RT_KD3_BOUNDS(64 * kd3_waves(16)) void k_shadow_kd3(TraceParams P) {
+    constexpr int kRays = 16, kCap = pool_cap_for<kRays>(), kRayVec = 5;
+    using RL = RayLayout<kRays>;
+    __shared__ WaveLds<kRays, kCap, kRayVec> s_lds[kd3_waves(kRays)];
+    const int wv = wave_id(), lane = (int)threadIdx.x & 63;
+    const int32_t b = (int32_t)blockIdx.x, ntiles = P.tiles_x * P.block_rows;
+    if (b >= ntiles) return;
+    const int32_t ti = tile_index(P, b);
+    if ((uint32_t)ti >= (uint32_t)ntiles) return;  // (orders 0 and 1 are bijections; never index past the grid)
+    WaveLds<kRays, kCap, kRayVec>& S_ = s_lds[wv];
+    const Unit U = unit_of_tile(P, ti, wv);
+    Pixel px;
+    const bool live = unit_pixel(P, U, kRays / 8, lane, px);
+    const int64_t h = live ? P.hit[px.out] : (int64_t)-1;
+    const bool own = h >= P.hit_base && h < P.hit_base + (int64_t)P.ntri;
+    const bool test = live && h >= 0 && !(P.shadow_skip_own && own);
+    if (__ballot(test) == 0ull) return;
+    const float d = test ? P.aov[px.out] : 0.0f;
+    float cam[3];
+    Ray R;
+    camera_ray(P, px, test, cam, R);
+    // the shadow segment of the stored hit: from the light to H = d*r - od
+    Ray Sh;
+    Sh.odx = -2.0f; Sh.ody = -2.0f; Sh.odz = -2.0f;
+    Sh.rx = 1.0f; Sh.ry = 1.0f; Sh.rz = 1.0f;
+    float lmax = 0.0f;
+    if (test) {
+        float sx = ((d * R.rx) - R.odx) - 2;
+        float sy = ((d * R.ry) - R.ody) - 2;
+        float sz = ((d * R.rz) - R.odz) - 2;
+        lmax = sqrtf((sx * sx) + (sy * sy) + (sz * sz)) * 0.9990234375f;  // correctly rounded sqrt
+        const float r = rsqrt21(sx, sy, sz);
+        Sh.rx = sx * r; Sh.ry = sy * r; Sh.rz = sz * r;
+    }
+    finish_ray(Sh);
+    if (lane < kRays) {
+        store_ray(&S_.ray[lane], RL::kStride, Sh, true, lmax, own ? (uint32_t)(h - P.hit_base) : kMiss);
+        S_.key[lane] = ~0ull;
+        S_.tri[lane] = kMiss;
+    }
+    __builtin_amdgcn_wave_barrier();
+    Counts C;
+    uint32_t iters = 0, popped = 0;
+    const int n = seed_root<kCount, true>(P, S_.items, Sh, test, lane, C.n_int, C.n_desc, lmax);
+    pool_walk<kCap, RL::kStride, true, kCount, true, kOrder>(P, S_.items, S_.ray, S_.key, S_.tri, n, lane, iters, popped,
+                                                            C.n_int, C.n_leaf, C.n_acc, C.n_desc);
+    if (test && S_.key[lane] == 0ull) P.argb[px.out] = 0x00000000u;
+    if (kCount) {  // a counted shadow walk's visits; [3] (hit pixels) is the render's
+        wave_count_add(&P.counters[0], C.n_int);
+        wave_count_add(&P.counters[1], C.n_leaf);
+        wave_count_add(&P.counters[2], C.n_acc);
+        wave_count_add(&P.counters[4], C.n_desc);
+    }
+}
+
 // The coarse groups (every 8x8 group of this rank outside the fine tiles),
 // P.coarse_per_wave (<= kCoarseMax) per wave.  A separate kernel: looping trace_unit inside
 // the fine kernel costs it a third of its occupancy (80 -> 113 VGPRs).
@@ -3093,6 +3173,29 @@ TraceFn kd_kernel(int version, int rays, int shadow, bool coarse) {
         case 1: return kd3_kernel<T, H, C, 2>(rays, coarse);
         case 2: return kd3_kernel<T, H, C, 3>(rays, coarse);
         default: return kd3_kernel<T, H, C, 4>(rays, coarse);
+        }
+    }
+}
+
+// k_shadow_kd3's instances, count x push order (any_order as kd_kernel's
+// shadow: 0..3, + 4 for counting walks that stop at occluders; the other
+// counting walks are not cut short, so one instance serves them).
+template <bool C>
+TraceFn shadow_kernel(int any_order) {
+    if constexpr (C) {
+        switch (any_order) {
+        case 4: return k_shadow_kd3<true, 4>;
+        case 5: return k_shadow_kd3<true, 5>;
+        case 6: return k_shadow_kd3<true, 6>;
+        case 7: return k_shadow_kd3<true, 7>;
+        default: return k_shadow_kd3<true, 0>;
+        }
+    } else {
+        switch (any_order & 3) {
+        case 0: return k_shadow_kd3<false, 0>;
+        case 1: return k_shadow_kd3<false, 1>;
+        case 2: return k_shadow_kd3<false, 2>;
+        default: return k_shadow_kd3<false, 3>;
         }
     }
 }

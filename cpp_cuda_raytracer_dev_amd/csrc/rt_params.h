@@ -121,6 +121,9 @@ struct TraceParams {
     // the split planes from the record's child boxes; null for every other
     // tree.  Last for the same reason as the planes.
     const float2* split_planes;
+    // rt_shadow_over (k_shadow_kd3 alone reads it; last for the same reason):
+    // the object's own pixels, hit_base <= hit < hit_base + ntri, are not tested
+    int32_t shadow_skip_own;
 };
 
 // Blocks of k_trace_kd3's grid (fine tiles, split extras, far fill).

@@ -450,6 +450,40 @@ class Camera:
         _lib.call("rt_render_over", self._h, _lib.ptr(xf), mode, flags, t, a, h, int(hit_base), s)
         return 0
 
+    def shadow_over(self, argb=None, hit=None, xform=None, flags=0, tile=None, hit_base=0, skip_own=False,
+                    stream=None) -> int:
+        """rt_shadow_over: the deferred shadow pass of this camera's object
+        over the composite in the targets (argb / hit: torch tensors or raw
+        pointers, None = the camera's own; planes: ``set_aov`` or the camera's
+        own): every hit pixel this object shadows becomes 0x00000000, and
+        nothing else is written.  hit_base: this object's base in the hit
+        buffer; skip_own: leave its own pixels out (their render ran with
+        RT_FLAG_SHADOW)."""
+        own = getattr(self, "_targets", (None, None))  # a layer camera: its base's buffers
+        if argb is None:
+            argb, hit = own[0], own[1] if hit is None else hit
+        xf = np.ascontiguousarray(xform if xform is not None else Quaternion().xform(), np.float32)
+        t = None if tile is None else C.byref(_lib.RtTile(tile[0], tile[1]))
+        s = C.c_void_p(stream) if isinstance(stream, int) else C.c_void_p(None)
+        a = argb if isinstance(argb, C.c_void_p) else _lib.ptr(argb)
+        h = hit if isinstance(hit, C.c_void_p) else _lib.ptr(hit)
+        _lib.call("rt_shadow_over", self._h, _lib.ptr(xf), flags, t, a, h, int(hit_base), int(bool(skip_own)), s)
+        return 0
+
+    def shadow_layers(self, flags=0, skip_own=False) -> int:
+        """The objects of this camera's frame shadow one another: after the
+        renders (``obj1.render; obj2.render``), one ``shadow_over`` for the
+        base object and one for each layer (``add_layer``) over the shared
+        targets, each with that object's current transform and hit base."""
+        if not self.object_list:
+            raise _lib.RtError("Camera.shadow_layers", -5, "add the base object (add_object) first")
+        base = self.object_list[-1]
+        self.shadow_over(None, None, base.quat.xform(), flags, hit_base=base.hit_base, skip_own=skip_own)
+        for layer in self._layers.values():
+            obj = layer.object_list[-1]
+            layer.shadow_over(None, None, obj.quat.xform(), flags, hit_base=obj.hit_base, skip_own=skip_own)
+        return 0
+
     def clear_layers(self, argb=None, hit=None, flags=0, tile=None, stream=None) -> int:
         """rt_render_clear: the miss state (background, hit -1, d = 400, zeros)
         into the targets, the order-free start of a composite."""

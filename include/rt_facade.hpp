@@ -278,6 +278,24 @@ public:
             }
         return RT_ERR_STATE;
     }
+    // Lets the frame's objects shadow one another (rt_shadow_over): after the
+    // renders, one deferred shadow pass for the base object and one for each
+    // layer over the shared buffers, each with that object's current
+    // transform and hit base.  obj1->render; obj2->render; shadow_layers();
+    // color_pixels gives the cross-shadowed frame.
+    int shadow_layers(bool skip_own = false) {
+        if (objects_.empty()) return RT_ERR_STATE;
+        u32* argb = nullptr;
+        s64* hit = nullptr;
+        int rc = rt_camera_targets(cam_, &argb, (int64_t**)&hit, nullptr, nullptr);
+        const Object* base = objects_.back();
+        if (!rc) rc = rt_shadow_over(cam_, base->quat->rot_m, 0u, nullptr, argb, (int64_t*)hit, base->hit_base,
+                                     skip_own ? 1 : 0, nullptr);
+        for (size_t k = 0; !rc && k < layers_.size(); k++)
+            rc = rt_shadow_over(layers_[k].cam, layers_[k].obj->quat->rot_m, 0u, nullptr, argb, (int64_t*)hit,
+                                layers_[k].obj->hit_base, skip_own ? 1 : 0, nullptr);
+        return rc;
+    }
     bool is_layer(const Object* o) const {
         for (auto& l : layers_)
             if (l.obj == o) return true;

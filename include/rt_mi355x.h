@@ -264,11 +264,53 @@ int rt_render_display(rt_camera* c, const float* xform, uint32_t mode, uint32_t 
  * Our definition (the reference builds a second object, TD/WinMain.cpp:152-
  * 156, but its render is commented out, :214-215, so it has no working second
  * object to match): the compared quantity is the stored ray parameter
- * d_dist.d; objects do not shadow one another; rt_comm_gather_frame's
- * rectangle is one object's, so a multi-GPU composite gathers whole packed
- * buffers and assembles them with rt_unpack_bands. */
+ * d_dist.d; RT_FLAG_SHADOW here finds occluders in this object's own tree
+ * only, and objects shadow one another through rt_shadow_over, a pass after
+ * the overs; rt_comm_gather_frame's rectangle is one object's, so a multi-GPU
+ * composite gathers whole packed buffers and assembles them with
+ * rt_unpack_bands. */
 int rt_render_over(rt_camera* c, const float* xform, uint32_t mode, uint32_t flags, const rt_tile* tile,
                    uint32_t* d_argb, int64_t* d_hit, int64_t hit_base, void* stream);
+
+/* The deferred shadow pass of a composite: lets object B (camera c, with its
+ * transform xform) cast shadows on whatever the composite shows.  With
+ * hit[p] the owner index in the hit target and d the float in plane 0 of c's
+ * plane target (bound or own) at pixel p, a pixel is tested iff hit[p] >= 0
+ * (with skip_own != 0: and p is not B's own pixel, hit_base <= hit[p] <
+ * hit_base + B's triangle count; use it when the overs ran with
+ * RT_FLAG_SHADOW).  B shadows p iff B's shadow test, the one RT_FLAG_SHADOW
+ * runs, finds an occluder for (p, d): from p's primary ray and xform form B's
+ * object-space ray (r, od) as B's nearest-hit walk does; walk the segment from
+ * the light (2,2,2) to H = d*r - od through B's tree with the segment rule (a
+ * box is entered only below Lmax = 0.9990234375 * |segment|) and the leaf
+ * rule (w < Lmax); the one excluded triangle is hit[p] - hit_base when p is
+ * B's own pixel, and none for any other pixel.  The frame gets 0x00000000 at
+ * every tested pixel B shadows, and the pass issues no other store at all:
+ * none to the frame elsewhere, none to the hit buffer, none to the planes.
+ * So it is idempotent, and the passes of several occluders commute.
+ * Consequences: for B's own pixels the test is bit for bit RT_FLAG_SHADOW's;
+ * with B at the identity H is the composite's hit point relative to the eye;
+ * under a transform B's light moves with B, as it does for B's own shadows.
+ * Our definition (the reference has neither shadows nor a working second
+ * object).
+ * Pixels and indices follow rt_render_over's rule (the packed band slot under
+ * a tile, the frame position under RT_FLAG_FRAME_OUT or without a tile).
+ * Flags: RT_FLAG_COUNT (the walk's visits go to c's counters [0], [1], [2],
+ * [4] as a counted shadow walk adds them, debug bit 16 included; [3] is not
+ * touched) and RT_FLAG_FRAME_OUT; any other, or hit_base < 0, returns
+ * RT_ERR_INVALID.  KD tree and kernel 3 only: RT_ERR_INVALID under
+ * RT_OPT_KERNEL 2, RT_ERR_STATE without a tree; how the pixel's owner was
+ * rendered (kernel 2, flat, another scene) does not matter.  d_argb and d_hit
+ * NULL: the camera's own buffers; d_argb given with d_hit NULL is
+ * RT_ERR_INVALID (the owner is needed).  Own planes never filled:
+ * RT_ERR_STATE; a bound stride below the pixels addressed: RT_ERR_INVALID.
+ * Nothing is launched on an error.  RT_OPT_SHADOW_ORDER (-1: the order in
+ * use, no timing frames here), RT_OPT_ITEMS and RT_OPT_POOL_CAP apply; the
+ * walk takes the double forms.  The depth is the caller's data: any bit
+ * pattern in plane 0 terminates with device error 0, and a NaN d shadows
+ * nothing. */
+int rt_shadow_over(rt_camera* c, const float* xform, uint32_t flags, const rt_tile* tile,
+                   uint32_t* d_argb, int64_t* d_hit, int64_t hit_base, int32_t skip_own, void* stream);
 
 /* The miss state into the same targets, for the pixels a render with that
  * tile and RT_FLAG_FRAME_OUT setting (the only flag accepted) addresses: argb

@@ -3,7 +3,10 @@
 splits the .hip_fatbin section into its offload bundles, unbundles each
 gfx950 code object and reads its AMDGPU metadata notes.
 
-    python tools/kernel_resources.py [lib.so] [--match k_trace_kd3]
+    python tools/kernel_resources.py [lib.so] [--match k_trace_kd3] [--against parent.so]
+
+--against: list only the entries that the other library does not have with
+the same figures (as multisets of lines), after one line that counts both.
 """
 import argparse
 import os
@@ -50,16 +53,13 @@ def occupancy(cur):
     return f"waves/SIMD {min(by_vgpr, by_lds)} (vgpr {by_vgpr}, lds {by_lds})"
 
 
-def main():
-    ap = argparse.ArgumentParser()
-    ap.add_argument("lib", nargs="?", default=os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))),
-                                                          "cpp_cuda_raytracer_dev_amd", "librt_mi355x.so"))
-    ap.add_argument("--match", default="k_trace_kd3")
-    a = ap.parse_args()
+def listing(lib, match):
+    """One line per kernel entry of lib whose name contains match."""
     fields = (".name", ".vgpr_count", ".sgpr_count", ".vgpr_spill_count", ".sgpr_spill_count",
               ".group_segment_fixed_size", ".private_segment_fixed_size")
+    out = []
     with tempfile.TemporaryDirectory() as d:
-        for k, co in enumerate(code_objects(a.lib)):
+        for k, co in enumerate(code_objects(lib)):
             p = os.path.join(d, f"co{k}")
             open(p, "wb").write(co)
             notes = subprocess.run([f"{LLVM}/llvm-readelf", "--notes", p], capture_output=True, text=True).stdout
@@ -70,11 +70,38 @@ def main():
                     if line.startswith(f + ":"):
                         cur[f] = line.split(":", 1)[1].strip()
                 if len(cur) == len(fields):
-                    if a.match in cur[".name"]:
-                        print(f"vgpr {cur['.vgpr_count']:>4} sgpr {cur['.sgpr_count']:>4} spill v{cur['.vgpr_spill_count']}"
-                              f"/s{cur['.sgpr_spill_count']} lds {cur['.group_segment_fixed_size']:>6} "
-                              f"scratch {cur['.private_segment_fixed_size']:>4}  {occupancy(cur)}  {cur['.name']}")
+                    if match in cur[".name"]:
+                        out.append(f"vgpr {cur['.vgpr_count']:>4} sgpr {cur['.sgpr_count']:>4} spill v{cur['.vgpr_spill_count']}"
+                                   f"/s{cur['.sgpr_spill_count']} lds {cur['.group_segment_fixed_size']:>6} "
+                                   f"scratch {cur['.private_segment_fixed_size']:>4}  {occupancy(cur)}  {cur['.name']}")
                     cur = {}
+    return out
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("lib", nargs="?", default=os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))),
+                                                          "cpp_cuda_raytracer_dev_amd", "librt_mi355x.so"))
+    ap.add_argument("--match", default="k_trace_kd3")
+    ap.add_argument("--against", default="", help="another build of the library: list only what differs from it")
+    a = ap.parse_args()
+    ap_lines = listing(a.lib, a.match)
+    if a.against:
+        from collections import Counter
+        other = listing(a.against, a.match)
+        left = Counter(other)
+        new = []
+        for line in ap_lines:
+            if left[line] > 0:
+                left[line] -= 1
+            else:
+                new.append(line)
+        gone = sum(left.values())
+        print(f"# {len(other)} entries in the other library, {len(other) - gone} of them here with identical figures, "
+              f"{gone} changed or gone; {len(new)} entries only here:")
+        ap_lines = new
+    for line in ap_lines:
+        print(line)
 
 
 if __name__ == "__main__":

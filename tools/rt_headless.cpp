@@ -1,7 +1,7 @@
 // rt_headless.cpp -- the headless frame loop that replaces WinMain
 // (TD/WinMain.cpp:44-249), written against the reference-shaped C++ facade.
 //
-//   rt_headless <mesh.ply> <mode 0|1|2> [w h frames out.ppm flat keys] [--aov planes.f32] [--over KEYS]
+//   rt_headless <mesh.ply> <mode 0|1|2> [w h frames out.ppm flat keys] [--aov planes.f32] [--over KEYS [--cross-shadow]]
 //
 // keys: held keys per frame, cycled, one input tick per frame (WinMain ticks
 // at TICK_RATE, :173): letters of R W S Q E T, '+' joins keys held together,
@@ -51,8 +51,17 @@ int main(int argc, char** argv) {
     // builds and never renders (:152-156, :214-215), is a layer of the frame
     // (Camera::add_layer): the same mesh posed by these key ticks, applied
     // once, and rendered over the first object every frame
+    // --cross-shadow (anywhere on the line, with --over): after the two
+    // renders of a frame the objects shadow one another (Camera::shadow_layers)
     const char* aov_out = nullptr;
     const char* over_keys = nullptr;
+    bool cross_shadow = false;
+    for (int k = 1; k < argc;) {
+        if (std::strcmp(argv[k], "--cross-shadow")) { k++; continue; }
+        cross_shadow = true;
+        for (int j = k; j + 1 < argc; j++) argv[j] = argv[j + 1];
+        argc -= 1;
+    }
     for (int k = 1; k + 1 < argc;) {
         const bool aov = !std::strcmp(argv[k], "--aov"), over = !std::strcmp(argv[k], "--over");
         if (!aov && !over) { k++; continue; }
@@ -60,8 +69,9 @@ int main(int argc, char** argv) {
         for (int j = k; j + 2 < argc; j++) argv[j] = argv[j + 2];
         argc -= 2;
     }
-    if (argc < 3) {
-        std::fprintf(stderr, "usage: %s mesh.ply mode [w h frames out.ppm flat keys] [--aov planes.f32] [--over KEYS]\n",
+    if (argc < 3 || (cross_shadow && !over_keys)) {
+        std::fprintf(stderr, "usage: %s mesh.ply mode [w h frames out.ppm flat keys] [--aov planes.f32] "
+                             "[--over KEYS [--cross-shadow]]\n",
                      argv[0]);
         return 2;
     }
@@ -124,6 +134,10 @@ int main(int argc, char** argv) {
         }
         if (obj1->render(main_cam, render_mode) || (over_keys && obj2->render(main_cam, render_mode))) {
             std::fprintf(stderr, "render: %s\n", rt_last_error_string());
+            return 1;
+        }
+        if (cross_shadow && main_cam->shadow_layers()) {
+            std::fprintf(stderr, "shadow_layers: %s\n", rt_last_error_string());
             return 1;
         }
         if (main_cam->color_pixels(PHONG_COLOR_TAG)) {
