@@ -33,16 +33,28 @@ them is a Python literal and a JSON value):
   ("sync", s)                          stream s synchronised, -1: the device
   ("render", ci, mode, flags, target)  target: ("own",) | ("into", s) | ("ranks", nranks, s)
                                        | ("over", mesh2, s) | ("display", s)
+                                       | ("xshadow", mesh2, s, skip_own, first)
                                        (s: one of NSTREAMS torch streams; "own": Object.render into the
                                        camera's buffers; "ranks": every rank's band tile, then unpack_bands;
                                        "over": clear_layers, render_over, add_object(mesh2), render_over;
-                                       "display": render_display against oracle.Window)
+                                       "display": render_display against oracle.Window;
+                                       "xshadow": the "over" target, then the two objects' deferred shadow
+                                       passes (Camera.shadow_over) over the same targets on stream s, each
+                                       object attached again for its pass with the transform it was rendered
+                                       with and its hit base, object `first` (0: the base, 1: mesh2) first;
+                                       with skip_own the two renders carry SHADOW; flags: COUNT or none; the
+                                       camera then shows mesh2 at the identity, as "over" leaves it.  KD only:
+                                       the generator emits a flat one only with skip_own, whose flat SHADOW
+                                       render is the rejection "xshadow_flat")
+  ("shadow", ci, s)                    Camera.shadow_over with no targets: the pass over the camera's own
+                                       frame, hit index and planes (rejected until a render filled the planes)
   ("loop", ci, mode, flags, nframes, inflight, nbuf, s)   FrameLoop.run
 """
 import numpy as np
 
 from oracle import _oracle as O, motion as M, np_oracle as N
 from tests import helpers as H, synth as S
+from tests.synth import SPLIT_FIELD_VARIANTS
 
 F = np.float32
 D = np.float64
@@ -78,10 +90,13 @@ TICKS = (M.KEY_W, M.KEY_R, M.KEY_W | M.KEY_Q, M.KEY_T | M.KEY_S, M.KEY_E, M.KEY_
 IDENT = tuple(float(x) for x in N.IDENT)
 
 REJECTIONS = ("opt_value", "opt_retired", "tree_dup", "tree_bfs", "tree_count", "shadow_flat", "shadow_k2", "flags_high",
-              "loop_aov")
+              "loop_aov", "xshadow_flat", "xshadow_k2", "xshadow_flags", "shadow_unfilled")
+#: the RtError code include/rt_mi355x.h documents for the deferred pass's rejections (RT_ERR_INVALID -1, RT_ERR_STATE -5)
+REJECT_CODES = {"xshadow_flat": -1, "xshadow_k2": -1, "xshadow_flags": -1, "shadow_unfilled": -5}
 STATE_KINDS = ("opt", "opt_bad", "sopt", "tree", "tree_bad", "build", "attach", "xf", "tick", "sync", "loop")
-TARGETS = ("own", "into", "ranks", "over", "display")
-RENDER_KINDS = tuple(f"{t}/{m}" for t in TARGETS + ("loop",) for m in ("kd", "flat"))
+TARGETS = ("own", "into", "ranks", "over", "display", "xshadow")
+RENDER_KINDS = tuple(f"{t}/{m}" for t in TARGETS + ("loop",) for m in ("kd", "flat") if (t, m) != ("xshadow", "flat"))
+XSHADOW_CAM0_CAP = 2               # "xshadow" renders per sequence on the 96x54 camera (the numpy reference's cost)
 SEEDS = (101, 102, 103, 104, 105, 106, 107, 108)
 
 
@@ -138,11 +153,13 @@ class Exp:
       rkind    a render's / loop's RENDER_KINDS entry
       layers   a valid render's frames: [(spec, hit_base)], spec = (mesh, tree,
                ci, transform, mode, shadow) (Oracle.frame / Oracle.planes)
-      snap     the camera state a render ran in (conditions of test_seq_cpu.py)"""
+      snap     the camera state a render ran in (conditions of test_seq_cpu.py)
+      xshadow  None, or (skip_own, first) of a composite whose deferred shadow
+               passes ran (the frame is then Oracle.cross's)"""
 
-    def __init__(self, op, kind, reject=None, cams=(), rkind=None, layers=(), snap=None):
+    def __init__(self, op, kind, reject=None, cams=(), rkind=None, layers=(), snap=None, xshadow=None):
         self.op, self.kind, self.reject, self.cams, self.rkind = op, kind, reject, tuple(cams), rkind
-        self.layers, self.snap = list(layers), snap
+        self.layers, self.snap, self.xshadow = list(layers), snap, xshadow
 
 
 class _Cam:
@@ -153,6 +170,8 @@ class _Cam:
         self.xf = IDENT
         self.motion = None
         self.gen = 0           # bumps whenever anything a render of this camera depends on changes
+        self.aov_filled = False   # a render wrote the camera's own planes (never cleared)
+        self.own = dict(argb=None, hit=None, aov=None)   # the specs the camera's own buffers hold
 
 
 class Model:
@@ -190,11 +209,28 @@ class Model:
             return "shadow_k2"
         return None
 
+    def xshadow_reject(self, ci, mode, flags, skip_own):
+        """An "xshadow" render's rejection, by the first call that fails: the
+        render (flags_high; xshadow_flat: SHADOW in flat mode) or the pass
+        (xshadow_k2: kernel 2; xshadow_flags: any flag but COUNT / FRAME_OUT)."""
+        if flags & ~31:
+            return "flags_high"
+        if mode != KD:
+            assert skip_own, "a flat xshadow without skip_own is not an operation"
+            return "xshadow_flat"
+        if self.cams[ci].opts[K_KERNEL] != 3:
+            return "xshadow_k2"
+        if flags & ~(COUNT | 8):
+            return "xshadow_flags"
+        assert not flags & 8, "RT_FLAG_FRAME_OUT is not generated"
+        return None
+
     def _snap(self, ci, mode, flags, nranks=1, stream=None):
         c = self.cams[ci]
         o = c.opts
         return dict(ci=ci, mesh=c.mesh, tree=self.tree[c.mesh], kernel=o[K_KERNEL], order=o[K_ORDER], flat=o[K_FLAT],
-                    mode=mode, flags=flags, stream=stream, gen=c.gen, xf=c.xf,
+                    mode=mode, flags=flags, stream=stream, gen=c.gen, xf=c.xf, shadow_order=o[K_SHADOW_ORDER],
+                    items=o[K_ITEMS], pool=o[K_POOL], debug=o[K_DEBUG],
                     grid=(c.mesh, c.xf, o[K_KERNEL], o[K_RAYS], o[K_COARSE], o[K_DEBUG], mode, nranks))
 
     def _spec(self, ci, mode, flags):
@@ -261,11 +297,28 @@ class Model:
             assert c.mesh is not None and mode in (KD, FLAT) and target[0] in TARGETS
             rkind = f"{target[0]}/{'flat' if mode else 'kd'}"
             nranks = target[1] if target[0] == "ranks" else 1
-            snap = self._snap(ci, mode, flags, nranks, target[-1] if target[0] != "own" else None)
+            snap = self._snap(ci, mode, flags, nranks, target[2] if target[0] == "xshadow" else
+                              target[-1] if target[0] != "own" else None)
+            if target[0] == "xshadow":
+                _, mesh2, _, skip_own, first = target
+                rej = self.xshadow_reject(ci, mode, flags, skip_own)
+                if rej:
+                    return Exp(op, "render", rej, cams=[ci], rkind=rkind, snap=snap)
+                rflags = flags | (SHADOW if skip_own else 0)
+                layers = [(self._spec(ci, mode, rflags), 0)]
+                self._attach(ci, mesh2)           # the second layer's object, at the identity
+                layers.append((self._spec(ci, mode, rflags), NTRI[layers[0][0][0]]))
+                return Exp(op, "render", cams=[ci], rkind=rkind, layers=layers, snap=snap, xshadow=(skip_own, first))
             rej = self.render_reject(ci, mode, flags)
             if rej:
                 return Exp(op, "render", rej, cams=[ci], rkind=rkind, snap=snap)
             layers = [(self._spec(ci, mode, flags), 0)]
+            if target[0] == "own":
+                c.own["argb"] = layers[0][0]
+                if flags & (HIT | AOV):           # (the planes ride on the write-hit instances)
+                    c.own["hit"] = layers[0][0][:5]
+                if flags & AOV:
+                    c.own["aov"], c.aov_filled = layers[0][0][:5], True
             if target[0] == "over":
                 base = NTRI[c.mesh]
                 self._attach(ci, target[1])       # the second layer's object, at the identity
@@ -281,6 +334,19 @@ class Model:
             if rej:
                 return Exp(op, "loop", rej, cams=[ci], rkind=rkind, snap=snap)
             return Exp(op, "loop", cams=[ci], rkind=rkind, layers=[(self._spec(ci, mode, flags), 0)], snap=snap)
+        if k == "shadow":
+            _, ci, s = op
+            c = self.cams[ci]
+            if c.opts[K_KERNEL] != 3:
+                return Exp(op, "shadow", "xshadow_k2", cams=[ci])
+            if not c.aov_filled:
+                return Exp(op, "shadow", "shadow_unfilled", cams=[ci])
+            spec = c.own["argb"]
+            # the camera's own frame, hit index and planes are one KD render's, of the object it shows now
+            assert spec is not None and c.own["hit"] == c.own["aov"] == spec[:5] and spec[4] == KD, (op, c.own)
+            assert spec[:4] == (c.mesh, self.tree[c.mesh], ci, c.xf), (op, spec)
+            c.own["argb"] = spec[:5] + (True,)
+            return Exp(op, "shadow", cams=[ci], layers=[(c.own["argb"], 0)])
         raise ValueError(f"unknown operation {op!r}")
 
 
@@ -298,6 +364,7 @@ class _Gen:
         self.seed = seed
         self.m = Model()
         self.ops = []
+        self.x0 = 0            # "xshadow" renders on camera 0 so far (XSHADOW_CAM0_CAP)
 
     # -- helpers
     def pick(self, seq):
@@ -306,10 +373,16 @@ class _Gen:
     def emit(self, *op):
         e = self.m.step(op)
         self.ops.append(e.op)
+        if e.xshadow and e.op[1] == 0:
+            self.x0 += 1
         return e
 
     def cam(self):
         return int(self.rng.integers(len(CAMS)))
+
+    def xcam(self, need=1):
+        """A camera for `need` "xshadow" renders: the large one while its budget lasts."""
+        return self.cam() if self.x0 + need <= XSHADOW_CAM0_CAP else 1
 
     def flags(self, ci, mode, allow=(HIT, COUNT, SHADOW, AOV)):
         f = 0
@@ -320,9 +393,15 @@ class _Gen:
             f &= ~SHADOW
         return f
 
-    def target(self, kind=None):
-        kind = kind or self.pick(TARGETS)
+    def target(self, kind=None, ci=1):
+        if kind is None:
+            kind = self.pick(TARGETS)
+            if kind == "xshadow" and ci == 0 and self.x0 >= XSHADOW_CAM0_CAP:
+                kind = "over"
         s = int(self.rng.integers(NSTREAMS))
+        if kind == "xshadow":     # (257 triangles as the second layer of the large camera: the reference's slowest pair)
+            return ("xshadow", self.pick(MESHES[1:] if ci == 0 else MESHES), s, int(self.rng.integers(2)),
+                    int(self.rng.integers(2)))
         if kind == "own":
             return ("own",)
         if kind == "ranks":
@@ -333,7 +412,11 @@ class _Gen:
 
     def render(self, ci, kind=None, mode=None, flags=None, target=None):
         mode = self.pick((KD, KD, FLAT)) if mode is None else mode
-        target = target or self.target(kind)
+        target = target or self.target(kind, ci)
+        if target[0] == "xshadow":           # a valid one: KD, kernel 3, COUNT or no flag
+            assert ci == 1 or self.x0 < XSHADOW_CAM0_CAP
+            self.ensure(ci, K_KERNEL, (3,))
+            mode, flags = KD, self.pick((0, COUNT)) if flags is None else flags
         self.emit("render", ci, mode, self.flags(ci, mode) if flags is None else flags, target)
 
     def loop(self, ci, mode=None, inflight=None, flags=None, nframes=None):
@@ -363,11 +446,13 @@ class _Gen:
     def debug_value(self):
         return int(sum(b for b in DEBUG_BITS if self.rng.random() < 0.3))
 
-    def state_op(self, kind, ci):
+    def state_op(self, kind, ci, keep_kernel=False):
         """One state-changing operation of `kind` that bears on camera ci."""
         mesh = self.m.cams[ci].mesh
         if kind == "opt":
             key = self.pick(tuple(OPT_VALUES) + (K_DEBUG, K_ORDER, K_KERNEL))
+            while keep_kernel and key == K_KERNEL:
+                key = self.pick(tuple(OPT_VALUES))
             self.emit("opt", ci, key, self.debug_value() if key == K_DEBUG else self.pick(OPT_VALUES[key]))
         elif kind == "opt_bad":
             if self.rng.random() < 0.3:
@@ -447,11 +532,12 @@ class _Gen:
         for ci in range(len(CAMS)):
             if self.m.cams[ci].mesh != mesh:
                 self.emit("attach", ci, mesh)
+        single = ("own", "into", "ranks", "display")     # (a composite ends on another object)
         for ci in range(len(CAMS)):
-            self.render(ci, mode=KD)
+            self.render(ci, kind=self.pick(single), mode=KD)
         self.emit("sopt", mesh, S_ORDER, self.pick([v for v in (0, 1, 2) if v != self.m.sopts[mesh][S_ORDER]]))
         for ci in range(len(CAMS)):
-            self.render(ci, mode=KD)
+            self.render(ci, kind=self.pick(single), mode=KD)
 
     def ep_e(self):
         ci = self.cam()
@@ -521,8 +607,89 @@ class _Gen:
             else:
                 mode = self.pick((KD, FLAT))
                 flags = self.pick((32, 64, 128, 1 << 30)) | self.flags(ci, mode)
+            if target[0] == "xshadow":       # (the pass's own rejections are ep_reject_x's)
+                target = ("over",) + target[1:3]
             self.emit("render", ci, mode, flags, target)
             self.emit("render", ci, mode, self.flags(ci, mode) & ~SHADOW, target)
+
+    def ep_reject_x(self, kind):
+        """A rejected deferred pass, then a valid "xshadow" with the same targets."""
+        ci = self.xcam()
+        t = self.target("xshadow", ci)
+        if kind == "xshadow_flat":
+            self.emit("render", ci, FLAT, self.pick((0, COUNT)), t[:3] + (1, t[4]))
+        elif kind == "xshadow_k2":
+            self.ensure(ci, K_KERNEL, (2,))
+            self.emit("render", ci, KD, self.pick((0, COUNT)), t)
+        else:
+            self.ensure(ci, K_KERNEL, (3,))
+            self.emit("render", ci, KD, self.pick((HIT, SHADOW, AOV, HIT | COUNT, AOV | HIT | SHADOW)), t)
+        self.render(ci, target=t)
+
+    # -- episodes of the deferred shadow pass (test_seq_cpu.py's x_* conditions)
+    def xshadow(self, ci, mesh2=None, flags=None, skip_own=None, first=None, s=None):
+        t = self.target("xshadow", ci)
+        t = ("xshadow", t[1] if mesh2 is None else mesh2, t[2] if s is None else s, t[3] if skip_own is None else skip_own,
+             t[4] if first is None else first)
+        self.render(ci, mode=KD, flags=flags, target=t)
+
+    def ep_x_own(self):
+        """The pass over the camera's own buffers, right after the render that filled them."""
+        ci = self.cam()
+        self.ensure(ci, K_KERNEL, (3,))
+        self.emit("render", ci, KD, HIT | AOV | self.pick((0, COUNT, SHADOW)), ("own",))
+        self.emit("shadow", ci, int(self.rng.integers(NSTREAMS)))
+
+    def ep_x_timed(self):
+        """A timed round of the shadow push order (12 trial frames and the one
+        that reads them), then the passes under the order it chose."""
+        ci = self.xcam()
+        self.ensure(ci, K_KERNEL, (3,))
+        self.emit("opt", ci, K_SHADOW_ORDER, -1)
+        s = int(self.rng.integers(NSTREAMS))
+        self.emit("loop", ci, KD, SHADOW, int(self.rng.integers(13, 20)), 1, 1, s)
+        self.emit("sync", -1)
+        self.render(ci, mode=KD, flags=SHADOW | self.pick((0, HIT)), target=("into", s))
+        self.xshadow(ci, s=s)
+
+    def ep_x_cost(self):
+        """The passes between two cost-order renders of one grid."""
+        ci = self.xcam()
+        self.ensure(ci, K_KERNEL, (3,))
+        self.emit("opt", ci, K_ORDER, self.pick((3, 4)))
+        if self.m.cams[ci].xf != IDENT:
+            self.emit("xf", ci, "id")
+        t = ("into", int(self.rng.integers(NSTREAMS)))
+        self.render(ci, mode=KD, flags=self.pick((0, HIT, HIT | COUNT)), target=t)
+        self.xshadow(ci, mesh2=self.m.cams[ci].mesh)
+        self.render(ci, mode=KD, flags=self.pick((HIT, HIT | COUNT)), target=t)
+
+    def ep_x_after(self, kind):
+        """The passes right after a tree replacement (a split-field variant), a device build or a scene option."""
+        ci = self.xcam()
+        self.ensure(ci, K_KERNEL, (3,))
+        if kind == "tree":
+            if self.m.cams[ci].mesh != "s33":
+                self.emit("attach", ci, "s33")
+            self.emit("tree", "s33", self.pick([n for n in SPLIT_FIELD_VARIANTS if n != self.m.tree["s33"]]))
+        elif kind == "build":
+            self.emit("build", self.m.cams[ci].mesh)
+        else:
+            self.state_op("sopt", ci)
+        self.xshadow(ci)
+
+    def ep_x_opts(self):
+        """The passes under the smallest pool, one item per lane and debug bit 16."""
+        ci = self.xcam(3)
+        self.ensure(ci, K_KERNEL, (3,))
+        self.emit("opt", ci, K_POOL, 89)
+        self.xshadow(ci)
+        self.emit("opt", ci, K_ITEMS, 1)
+        self.xshadow(ci)
+        debug = self.m.cams[ci].opts[K_DEBUG]
+        self.emit("opt", ci, K_DEBUG, debug | 16)
+        self.xshadow(ci, flags=0)            # (a counted walk under bit 16 stops at occluders: no counters to compare)
+        self.emit("opt", ci, K_DEBUG, debug)
 
     def ep_ticks(self):
         """A moving object: a run of key ticks, a render after each."""
@@ -580,19 +747,29 @@ class _Gen:
             self.render(ci)
 
     def pair(self, skind, rkind):
-        ci = self.cam()
-        self.state_op(skind, ci)
+        if rkind.startswith("xshadow"):      # kernel 3 first: the state change is then the last thing before the passes
+            ci = self.xcam()
+            self.ensure(ci, K_KERNEL, (3,))
+            self.state_op(skind, ci, keep_kernel=True)
+        else:
+            ci = self.cam()
+            self.state_op(skind, ci)
         self.any_render(ci, rkind)
 
     def run(self):
         self.emit("attach", 0, "s257")
         self.emit("attach", 1, self.pick(("s33", "copies", "mat")))
+        self.emit("shadow", self.cam(), int(self.rng.integers(NSTREAMS)))   # nothing has filled the camera's own planes
         # every (state kind, render kind) pair once over eight consecutive seeds
         deck = [(s, r) for s in STATE_KINDS for r in RENDER_KINDS]
         np.random.default_rng(0x5E9).shuffle(deck)
         chunks = [lambda p=p: self.pair(*p) for p in deck[self.seed % 8::8]]
         chunks += [self.ep_a, self.ep_b, self.ep_c, self.ep_d, self.ep_e, self.ep_f, self.ep_h, self.ep_ticks]
-        chunks += [lambda k=k: self.ep_reject(k) for k in REJECTIONS]
+        chunks += [lambda k=k: self.ep_reject(k) for k in REJECTIONS if k not in REJECT_CODES]
+        chunks += [lambda k=k: self.ep_reject_x(k) for k in ("xshadow_flat", "xshadow_k2", "xshadow_flags")]
+        chunks += [self.ep_x_own, self.ep_x_opts]
+        chunks += [self.ep_x_timed, self.ep_x_cost]
+        chunks += [lambda k=k: self.ep_x_after(k) for k in (("tree", "build"), ("build", "sopt"), ("sopt", "tree"))[self.seed % 3]]
         settings = [(k, v) for k, vs in OPT_VALUES.items() for v in vs] + [(K_DEBUG, b) for b in DEBUG_BITS + (0,)]
         settings += [(K_DEBUG, 4 | 2048), (K_DEBUG, 8 | 64 | 256), (K_DEBUG, 1024 | 2048 | 4), (K_DEBUG, sum(DEBUG_BITS))]
         np.random.default_rng(0x0B7).shuffle(settings)
@@ -674,6 +851,7 @@ class Oracle:
     def __init__(self):
         self.w = world()
         self._scenes, self._frames, self._planes, self._prep, self._rays = {}, {}, {}, {}, {}
+        self._cross, self._xprep, self._xtraced = {}, {}, {}
 
     def _rad(self, mesh):
         return O.default_rad(NTRI[mesh]) if self.w.rad[mesh] is None else self.w.rad[mesh]
@@ -732,10 +910,58 @@ class Oracle:
             self._planes[key] = out
         return self._planes[key]
 
+    def cross(self, layers, fresh=False):
+        """The cross-shadowed frame of a composite's two layers [(spec, hit
+        base)] by the numpy reference (tests/test_xshadow_cpu.cross_shadow on
+        np_oracle.prepare of each spec's oracle tree and trace_object with the
+        mesh's radiance table) -> (pixel indices, argb, hit, foreign, own):
+        foreign[B] / own[B] the five counters of object B's shadow walks of the
+        other object's pixels / of its own.  Cached per pair of specs (the
+        shadow flag apart: the renders' own shadows are the passes' too);
+        fresh: every CROSS_FRESH_STEP-th pixel alone, nothing cached."""
+        from tests.test_xshadow_cpu import cross_shadow, trace_object
+        key = tuple(spec[:5] for spec, _ in layers)
+        if not fresh and key in self._cross:
+            return self._cross[key]
+        ci = key[0][2]
+        w, h = CAMS[ci]
+        cam = N.camera(w, h)
+        pixels = np.arange(0, w * h, CROSS_FRESH_STEP if fresh else 1)
+        Ps, traced = [], []
+        for mesh, tree, _, xf, mode in key:
+            assert mode == KD
+            pk = (mesh, tree, ci)
+            P = None if fresh else self._xprep.get(pk)
+            if P is None:
+                P = N.prepare(self.w.pts[mesh], N.nodes_from_array(self.w.otrees[mesh][tree]), cam)
+                if not fresh:
+                    self._xprep[pk] = P
+            Ps.append(P)
+            tk = (mesh, tree, ci, xf)
+            tr = None if fresh else self._xtraced.get(tk)
+            if tr is None:
+                tr = trace_object(P, cam, np.array(xf, F), pixels, rad=self.w.rad[mesh])
+                if not fresh:
+                    self._xtraced[tk] = tr
+            traced.append(tr)
+        foreign, own = [[0] * 5, [0] * 5], [[0] * 5, [0] * 5]
+        argb, hit, _, _ = cross_shadow(Ps, cam, [np.array(k[3], F) for k in key], pixels=pixels, traced=traced,
+                                       cnt=foreign, own_cnt=own)
+        assert [base for _, base in layers] == [0, NTRI[key[0][0]]]
+        out = (pixels, argb, hit, np.array(foreign, np.uint64), np.array(own, np.uint64))
+        for a in out:
+            a.setflags(write=False)
+        if not fresh:
+            self._cross[key] = out
+        return out
+
     def close(self):
         for sc in self._scenes.values():
             sc.close()
         self._scenes = {}
+
+
+CROSS_FRESH_STEP = 16
 
 
 def hit_planes(P, rays, X, mode, hit, rad):
@@ -783,12 +1009,27 @@ def expected(oracle, exp, fresh=False):
     """A valid render's expected (argb, hit, planes bits or None, counters):
     the oracle's frame, or the composite of its layers (tests/test_over_cpu.py)."""
     from tests.test_over_cpu import composite
-    flags, over = exp.op[3], exp.op[0] == "render" and exp.op[4][0] == "over"
+    if exp.kind == "shadow":     # the pass over the camera's own buffers: the shadow frame of the render they hold
+        f = oracle.frame(exp.layers[0][0], fresh)
+        return f[0], f[1], None, None
+    flags, over = exp.op[3], exp.op[0] == "render" and exp.op[4][0] in ("over", "xshadow")
     frames = [oracle.frame(spec, fresh) for spec, _ in exp.layers]
     cnt = np.sum([np.asarray(f[2][:5], np.uint64) for f in frames], axis=0)
     planes = [oracle.planes(spec, fresh) for spec, _ in exp.layers] if (flags & AOV or over) else None
     if over:
         argb, hit, pl = composite([(f[0], f[1], p, base) for f, p, (_, base) in zip(frames, planes, exp.layers)])
+        if exp.xshadow:
+            # the frame is cross_shadow's; hit index and planes are the composite's; the counters are the renders'
+            # (with their own shadow walks under skip_own) plus the passes': the other object's pixels, and the
+            # own ones unless skipped
+            pixels, xargb, xhit, foreign, own = oracle.cross(exp.layers)
+            assert (xhit == hit).all(), "the numpy composite's hit index differs from the C oracle's"
+            argb = xargb.copy()
+            if fresh:
+                pixels, fargb, fhit, _, _ = oracle.cross(exp.layers, fresh=True)
+                assert (fhit == hit[pixels]).all()
+                argb[pixels] = fargb
+            cnt = cnt + foreign.sum(0) + (0 if exp.xshadow[0] else own.sum(0))
         return argb, hit, pl, cnt
     return frames[0][0], frames[0][1], None if planes is None else planes[0], cnt
 
@@ -841,6 +1082,7 @@ class Runner:
         self.windows = [O.Window(w * h) for w, h in CAMS]
         self.bufs = {}
         self.renders = 0
+        self.passes = 0                         # deferred shadow passes among them (two per "xshadow", one per "shadow")
         self.done = []
         self.restores = [0] * len(CAMS)         # RT_OPT_ORDER_RESTORES as last read
         self.reprepared = [False] * len(CAMS)   # the camera's records follow a new object or tree
@@ -938,9 +1180,95 @@ class Runner:
         from cpp_cuda_raytracer_dev_amd import _lib
         try:
             fn()
-        except _lib.RtError:
+        except _lib.RtError as e:
+            code = REJECT_CODES.get(exp.reject)
+            assert code is None or e.code == code, f"{exp.reject}: RtError code {e.code}, documented {code}"
             return
         raise AssertionError(f"the call was accepted; the model expects it rejected ({exp.reject})")
+
+    def shadow_pass(self, ci, *args, **kw):
+        """Camera.shadow_over, which must leave what the renders' launch state
+        shows (RT_OPT_ORDER_RESTORES, RT_OPT_FINE_TILES) as it was."""
+        from cpp_cuda_raytracer_dev_amd import _lib
+        cam = self.cams[ci]
+        state = lambda: (cam.get_option(_lib.RT_OPT_ORDER_RESTORES), cam.get_option(_lib.RT_OPT_FINE_TILES))  # noqa: E731
+        before = state()
+        cam.shadow_over(*args, **kw)
+        assert state() == before, f"the deferred shadow pass changed the renders' state: {before} -> {state()}"
+
+    def op_xshadow(self, exp, xf, mesh):
+        """The "over" composite, then the two objects' passes over the same targets."""
+        from cpp_cuda_raytracer_dev_amd import _lib
+        torch = self.torch
+        _, ci, mode, flags, (_, mesh2, s, skip_own, first) = exp.op
+        cam = self.cams[ci]
+        w, h = CAMS[ci]
+        n = w * h
+        st = self.streams[s]
+        X, ident = np.array(xf, F), np.array(IDENT, F)
+        argb, hit, planes = self.targets(ci, "full", n)
+        self.poison(st, argb, hit, planes)
+        cam.set_aov(planes.view(torch.float32), n)
+        rflags = flags | (SHADOW if skip_own else 0)
+        if exp.reject:
+            if exp.reject in ("flags_high", "xshadow_flat"):     # the render is the call that fails
+                call = lambda: cam.render_over(argb, hit, xform=X, mode=mode, flags=rflags, hit_base=0,  # noqa: E731
+                                               stream=st.cuda_stream)
+            else:
+                call = lambda: cam.shadow_over(argb, hit, xform=X, flags=flags, hit_base=0, skip_own=bool(skip_own),  # noqa: E731
+                                               stream=st.cuda_stream)
+            self.expect_error(exp, call)
+            self.untouched(argb, hit, planes)
+            return
+        want = expected(self.oracle, exp)
+        cam.clear_layers(argb, hit, stream=st.cuda_stream)
+        cam.render_over(argb, hit, xform=X, mode=mode, flags=rflags, hit_base=0, stream=st.cuda_stream)
+        self.restores[ci] = cam.get_option(_lib.RT_OPT_ORDER_RESTORES)   # (the first layer may restore one)
+        self.attach(ci, mesh2)
+        cam.render_over(argb, hit, xform=ident, mode=mode, flags=rflags, hit_base=NTRI[mesh], stream=st.cuda_stream)
+        objects = ((mesh, X, 0), (mesh2, ident, NTRI[mesh]))
+        for k in (first, 1 - first):
+            m, Xk, base = objects[k]
+            self.attach(ci, m)
+            self.shadow_pass(ci, argb, hit, xform=Xk, flags=flags, hit_base=base, skip_own=bool(skip_own),
+                             stream=st.cuda_stream)
+        if first == 1:
+            self.attach(ci, mesh2)       # the camera shows mesh2 at the identity, as "over" leaves it
+        st.synchronize()
+        self.same("argb", self.host(argb), want[0])
+        self.same("hit", self.host(hit), want[1])
+        self.same("planes", self.host(planes).reshape(10, n), want[2])
+        if flags & COUNT and not exp.snap["debug"] & 16:   # (a counted walk under bit 16 stops at occluders)
+            self.counters(exp, want[3])
+        self.passes += 2
+        self.after_render(exp)
+
+    def op_shadow(self, exp):
+        """The pass over the camera's own frame, hit index and planes."""
+        from cpp_cuda_raytracer_dev_amd import _lib
+        _, ci, s = exp.op
+        cam = self.cams[ci]
+        w, h = CAMS[ci]
+        st = self.streams[s]
+        cam.set_aov(None)
+        frame = lambda: (np.zeros(w * h, np.uint32), np.zeros(w * h, np.int64))  # noqa: E731
+        before, after = frame(), frame()
+        _lib.call("rt_read_frame", cam._h, _lib.ptr(before[0]), _lib.ptr(before[1]))
+        if exp.reject:
+            self.expect_error(exp, lambda: cam.shadow_over(stream=st.cuda_stream))
+        else:
+            want = expected(self.oracle, exp)
+            self.shadow_pass(ci, xform=np.array(self.model.cams[ci].xf, F), stream=st.cuda_stream)
+            st.synchronize()
+        _lib.call("rt_read_frame", cam._h, _lib.ptr(after[0]), _lib.ptr(after[1]))
+        if exp.reject:
+            assert (before[0] == after[0]).all() and (before[1] == after[1]).all(), "a rejected pass wrote a frame"
+            return
+        self.same("argb", after[0], want[0])
+        self.same("hit", after[1], want[1])
+        assert cam.device_error() == 0, f"device error word {cam.device_error()}"
+        self.passes += 1
+        self.renders += 1
 
     def op_opt(self, exp):
         from cpp_cuda_raytracer_dev_amd import _lib
@@ -1002,6 +1330,8 @@ class Runner:
         w, h = CAMS[ci]
         n = w * h
         kind = target[0]
+        if kind == "xshadow":
+            return self.op_xshadow(exp, xf, mesh)
         st = self.streams[target[-1]] if kind != "own" else None
         X = np.array(xf, F)
         want = None if exp.reject else expected(self.oracle, exp)

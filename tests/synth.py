@@ -657,3 +657,121 @@ def tree_variants():
         keeps = bool((s1 == nodes["s1"][inner]).all() and (s2 == nodes["s2"][inner]).all())
         assert keeps == (name not in SPLIT_FIELD_VARIANTS), name
     return (v, f), out
+
+
+# ------------------------------------------- the deferred shadow pass (rt_shadow_over)
+# The pass walks another object's hit points (read back from plane 0) through
+# its own object's tree.  The tables below send the fused shadow walk's corpus
+# above through it (tests/test_gpu_xshadow_synth.py; the conditions are in
+# tests/test_synth_cpu.py).
+
+IDENT_XFS = (("identity", None),)
+#: the exponents of SCALE_EXPONENTS at which scaled_soup's shadow frame has a
+#: shadowed pixel (the light stays at eye + (2, 2, 2) while the scene shrinks:
+#: below 2^0 nothing lies between it and a hit; test_synth_cpu.py measures all)
+XSHADOW_SCALE_EXPONENTS = (7,)
+
+
+def twin_cases():
+    """The scenes of the twin passes: [(name, make() -> SynthScene, ((xform
+    name, xform), ...))], each scene at the identity and under the transforms
+    its fused shadow test renders it under."""
+    cases = [(f"light-{p}", lambda p=p: light_scene(p), IDENT_XFS + TREE_XFS) for p in LIGHT_POSE_NAMES]
+    cases += [(f"planes-{which}-{w}x{h}", lambda a=(which, w, h): light_planes_scene(*a), LIGHT_PLANE_XFS)
+              for which in LIGHT_PLANES for w, h in LIGHT_PLANE_FRAMES]
+    cases.append(("tie", lambda: SynthScene(*light_tie(), W, H_, cam_kw=THRESHOLD_CAM), IDENT_XFS))
+
+    def on_triangle():
+        v, f, kw = light_on_triangle()
+        return SynthScene(v, f, W, H_, cam_kw=kw)
+
+    cases.append(("on_triangle", on_triangle, IDENT_XFS))
+    cases += [(f"soup-{n}", lambda n=n: soup_scene(n), IDENT_XFS + TREE_XFS) for n in SOUP_NS]
+
+    def tree(name):
+        (v, f), trees = tree_variants()
+        return SynthScene(v, f, W, H_, nodes=trees[name])
+
+    cases += [(f"tree-{name}", lambda name=name: tree(name), IDENT_XFS + TREE_XFS)
+              for name in ("swapped", "inflated", "shrunk") + SPLIT_FIELD_VARIANTS]
+    cases += [(f"scaled-{e}", lambda e=e: scaled_soup(e), IDENT_XFS) for e in XSHADOW_SCALE_EXPONENTS]
+    return cases
+
+
+TWIN_CASES = {name: (make, xfs) for name, make, xfs in twin_cases()}
+
+#: two objects: light_scene(pose)'s soup(65) at the identity and the same soup
+#: as a layer at these offsets (X[3], X[7], X[11])
+XSHADOW_OFFSETS = ((0.2, -0.1, 0.05), (-0.05, 0.2, -0.15))
+#: (pose, offset index) -> (layer pixels shadowed by the base only, by both;
+#: base pixels shadowed by the layer only, by both) of 627, measured with
+#: test_xshadow_cpu.class_counts(cross_shadow(...)) (test_synth_cpu.py)
+XSHADOW_CLASSES = {
+    ("nnn", 0): (10, 15, 69, 70), ("nnn", 1): (40, 25, 26, 71), ("pnn", 0): (47, 8, 17, 17), ("pnn", 1): (26, 3, 36, 34),
+    ("npn", 0): (7, 24, 70, 60), ("npn", 1): (47, 25, 9, 23), ("ppn", 0): (19, 7, 44, 18), ("ppn", 1): (38, 3, 18, 9),
+    ("nnp", 0): (20, 9, 26, 12), ("nnp", 1): (20, 12, 52, 43), ("pnp", 0): (70, 19, 5, 10), ("pnp", 1): (4, 16, 61, 29),
+    ("npp", 0): (14, 27, 51, 61), ("npp", 1): (41, 20, 17, 39), ("ppp", 0): (27, 3, 4, 2), ("ppp", 1): (9, 5, 31, 7),
+    ("zpp", 0): (17, 13, 41, 15), ("zpp", 1): (37, 16, 12, 29), ("pzn", 0): (23, 10, 14, 4), ("pzn", 1): (16, 6, 24, 8),
+    ("npz", 0): (7, 36, 88, 72), ("npz", 1): (41, 16, 8, 31), ("zzp", 0): (22, 5, 18, 8), ("zzp", 1): (19, 4, 76, 18),
+    ("znz", 0): (26, 3, 10, 7), ("znz", 1): (18, 17, 61, 47), ("pzz", 0): (33, 8, 7, 10), ("pzz", 1): (11, 7, 20, 13),
+    ("inside", 0): (0, 0, 0, 0), ("inside", 1): (0, 0, 0, 0)}
+XSHADOW_POSE = "pnp"                             # the pose of the launch-parameter tests
+
+#: tiny occluders and receivers: soup(n) over / under soup(65) from the default
+#: camera, the layer at this offset
+XSHADOW_TINY_OFFSET = (0.15, 0.15, 0.15)
+#: n -> (class counts with soup(n) as the layer over soup(65), with soup(n) as
+#: the base under it), the classes of XSHADOW_CLASSES
+XSHADOW_TINY = {1: ((0, 0, 1, 1), (0, 0, 0, 0)), 2: ((0, 0, 1, 0), (0, 0, 13, 0)), 3: ((5, 0, 0, 2), (0, 0, 29, 0)),
+                4: ((0, 0, 8, 3), (1, 8, 7, 0)), 5: ((3, 0, 0, 1), (1, 0, 10, 0)), 8: ((9, 0, 47, 13), (2, 1, 21, 0)),
+                9: ((1, 1, 15, 9), (0, 2, 45, 3)), 33: ((5, 4, 110, 29), (29, 35, 81, 45)),
+                257: ((6, 96, 107, 39), (13, 7, 33, 205))}
+
+
+def np_scene(sc):
+    """np_oracle.prepare of a SynthScene's mesh, tree and camera."""
+    return N.prepare(sc.pts, N.nodes_from_array(sc.onodes), sc.np_camera())
+
+
+def segment_classes(P, d, rays):
+    """Where each shadow segment ends relative to the root box of the prepared
+    scene P (np_oracle.prepare), by the root's slab lines of np_oracle._walk:
+    d [m] the depths, rays [m] the object-space rays (r, od) of the occluder.
+    -> int [m]: 0 the segment ends before the box (the root's entry parameter
+    is at or beyond Lmax: the walk does not descend), 1 it ends inside the box,
+    2 it passes through and ends beyond it, -1 the light's ray misses the box
+    or starts inside it (no entry either way)."""
+    bo = P["vox"][0]["bo"]
+    out = np.full(len(d), -1, np.int64)
+    od = (F(-2), F(-2), F(-2))
+    with np.errstate(all="ignore"):
+        for j in range(len(d)):
+            r, o_ = rays[j]
+            sv = [F(F(F(d[j] * r[k]) - o_[k]) - F(2)) for k in range(3)]
+            L2 = F(F(F(sv[0] * sv[0]) + F(sv[1] * sv[1])) + F(sv[2] * sv[2]))
+            lmax = F(F(np.sqrt(np.float64(L2))) * N.SHADOW_SCALE)
+            s = N.dev_normalize(*sv)
+            inv = [F(F(1) / s[k]) for k in range(3)]
+            o = [F(od[k] / s[k]) for k in range(3)]
+            t0 = [F(bo[k] * inv[k]) if s[k] > 0 else F(bo[k + 3] * inv[k]) for k in range(3)]
+            t1 = [F(bo[k + 3] * inv[k]) if s[k] > 0 else F(bo[k] * inv[k]) for k in range(3)]
+            maxt0 = np.fmax(F(t0[2] + o[2]), np.fmax(F(t0[0] + o[0]), F(t0[1] + o[1])))
+            mint1 = np.fmin(F(t1[2] + o[2]), np.fmin(F(t1[0] + o[0]), F(t1[1] + o[1])))
+            if not (np.float64(mint1) >= np.float64(maxt0) - N.EPS and np.float64(maxt0) > -N.EPS):
+                continue
+            out[j] = 0 if not maxt0 < lmax else (1 if lmax <= mint1 else 2)
+    return out
+
+
+def pass_check(got_argb, got_cnt, want_argb, want_cnt, what=""):
+    """The comparison every counted pass goes through: the frame bit for bit;
+    counters [0] (interior visits), [1] (leaf visits) and [4] (descents) equal
+    to the reference's shadow walks', [2] as test_gpu_xshadow.counters_match
+    compares it (kernel 3 counts valid candidates: >= the DFS's accept events).
+    want_cnt None: an uncounted pass."""
+    got_argb, want_argb = np.asarray(got_argb).view(np.uint32), np.asarray(want_argb).view(np.uint32)
+    bad = np.flatnonzero(got_argb != want_argb)
+    assert bad.size == 0, (what, "argb", bad.size, bad[:8], got_argb[bad[:4]], want_argb[bad[:4]])
+    if want_cnt is not None:
+        got, want = [int(x) for x in got_cnt], [int(x) for x in want_cnt]
+        assert [got[k] for k in (0, 1, 4)] == [want[k] for k in (0, 1, 4)] and got[2] >= want[2], (what, got, want)

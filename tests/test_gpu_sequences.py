@@ -31,8 +31,8 @@ def test_sequence(oracle, seed):
     ops = Q.generate(seed)
     t0 = time.perf_counter()
     r = Q.replay(ops, seed=seed, oracle=oracle)
-    print(f"seed {seed}: {len(ops)} operations, {r.renders} compared renders and loops, "
-          f"{time.perf_counter() - t0:.2f} s")
+    print(f"seed {seed}: {len(ops)} operations, {r.renders} compared renders and loops "
+          f"({r.passes} deferred shadow passes among them), {time.perf_counter() - t0:.2f} s")
     assert len(r.done) == len(ops) and r.renders >= 60
 
 

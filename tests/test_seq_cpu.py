@@ -36,7 +36,13 @@ def _frames(e):
 
 
 def _is_over(e):
-    return e.kind == "render" and e.op[4][0] == "over"
+    """A composite: its second layer renders in a new attachment ("xshadow" as "over")."""
+    return e.kind == "render" and e.op[4][0] in ("over", "xshadow")
+
+
+def _is_x(e):
+    """A valid "xshadow": a composite whose deferred shadow passes ran."""
+    return e.kind == "render" and not e.reject and e.xshadow is not None
 
 
 def _periods(exps, ci):
@@ -187,7 +193,83 @@ def cond_h(exps):
     return False
 
 
-CONDITIONS = dict(a=cond_a, b=cond_b, c=cond_c, d=cond_d, e=cond_e, f=cond_f, g=cond_g, h=cond_h)
+# ---- the deferred shadow pass (rt_shadow_over) in the sequences
+
+def cond_x_timed(exps):
+    """The passes on a camera whose shadow push order is timed (-1) after a
+    round has chosen one: the camera's first 12 uncounted SHADOW frames under
+    -1 are the round's trials (kernel 3; single renders, or a loop with one
+    frame in flight), then the device is synchronised, then one more such
+    frame reads the result."""
+    for ci in range(len(Q.CAMS)):
+        trial, synced, chosen = 0, False, False
+        for e in exps:
+            if e.reject:
+                continue
+            if e.kind == "sync":
+                synced = synced or (trial >= 12 and e.op[1] == -1)
+            elif _is_x(e) and e.op[1] == ci:
+                if chosen and e.snap["shadow_order"] == -1:
+                    return True
+            elif _is_frame(e) and e.op[1] == ci:
+                s = e.snap
+                if (s["mode"] == Q.KD and s["kernel"] == 3 and s["shadow_order"] == -1 and s["flags"] & Q.SHADOW
+                        and not s["flags"] & Q.COUNT and (e.kind == "render" or s["inflight"] == 1)):
+                    chosen = chosen or synced
+                    trial += _frames(e)
+    return False
+
+
+def cond_x_cost(exps):
+    """The passes directly between two cost-order renders (tile order 3 or 4)
+    of the same grid: no operation but the "xshadow" between them."""
+    def cost(e):
+        return (e.kind == "render" and not e.reject and not _is_over(e) and e.snap["mode"] == Q.KD
+                and e.snap["kernel"] == 3 and e.snap["order"] in (3, 4))
+    for a, x, b in zip(exps, exps[1:], exps[2:]):
+        if cost(a) and _is_x(x) and cost(b) and a.op[1] == x.op[1] == b.op[1] and a.op[4] == b.op[4] \
+                and (a.snap["grid"], a.snap["order"]) == (b.snap["grid"], b.snap["order"]):
+            return True
+    return False
+
+
+def _x_right_after(kind):
+    def cond(exps):
+        return any(a.kind == kind and not a.reject and _is_x(x) and x.op[1] in a.cams for a, x in zip(exps, exps[1:]))
+    cond.__doc__ = f"The passes right after a valid `{kind}` that bears on their camera."
+    return cond
+
+
+def cond_x_split(exps):
+    """The passes with an occluder on a tree whose split fields differ from its children's bounds."""
+    return any(_is_x(e) and any(spec[1] in S.SPLIT_FIELD_VARIANTS for spec, _ in e.layers) for e in exps)
+
+
+def cond_x_pool(exps):
+    """The passes under RT_OPT_POOL_CAP 89."""
+    return any(_is_x(e) and e.snap["pool"] == 89 for e in exps)
+
+
+def cond_x_items(exps):
+    """The passes under RT_OPT_ITEMS 1."""
+    return any(_is_x(e) and e.snap["items"] == 1 for e in exps)
+
+
+def cond_x_debug16(exps):
+    """The passes with debug bit 16."""
+    return any(_is_x(e) and e.snap["debug"] & 16 for e in exps)
+
+
+def cond_x_own(exps):
+    """The pass over the camera's own buffers, accepted; and rejected before anything filled the planes."""
+    return (any(e.kind == "shadow" and not e.reject for e in exps)
+            and any(e.kind == "shadow" and e.reject == "shadow_unfilled" for e in exps))
+
+
+CONDITIONS = dict(a=cond_a, b=cond_b, c=cond_c, d=cond_d, e=cond_e, f=cond_f, g=cond_g, h=cond_h,
+                  x_timed=cond_x_timed, x_cost=cond_x_cost, x_tree=_x_right_after("tree"), x_build=_x_right_after("build"),
+                  x_sopt=_x_right_after("sopt"), x_split=cond_x_split, x_pool=cond_x_pool, x_items=cond_x_items,
+                  x_debug16=cond_x_debug16, x_own=cond_x_own)
 
 
 def pairs(exps):
@@ -232,7 +314,7 @@ def test_deterministic_literals(seed):
 
 def test_every_kind_occurs(traces):
     kinds = {e.kind for exps in traces.values() for e in exps}
-    assert kinds == set(Q.STATE_KINDS) | {"render"}, kinds
+    assert kinds == set(Q.STATE_KINDS) | {"render", "shadow"}, kinds
     for seed, exps in traces.items():
         assert {e.reject for e in exps if e.reject} == set(Q.REJECTIONS), seed
     rk = {e.rkind for exps in traces.values() for e in exps if _is_frame(e)}
@@ -242,7 +324,7 @@ def test_every_kind_occurs(traces):
         assert {o[3] for o in ops if o[0] == "opt" and o[2] == key} >= set(values), key
     debug = {o[3] for o in ops if o[0] == "opt" and o[2] == Q.K_DEBUG}
     assert all(any(v & b for v in debug) for b in Q.DEBUG_BITS) and 0 in debug
-    assert all(v & ~sum(Q.DEBUG_BITS) == 0 for v in debug)        # no other debug bit
+    assert all(v & ~(sum(Q.DEBUG_BITS) | 16) == 0 for v in debug)  # no other debug bit (16: around an uncounted "xshadow")
     assert {o[2] for o in ops if o[0] == "opt"} >= set(Q.OPT_RETIRED)
     assert {o[3] for o in ops if o[0] == "sopt" and o[2] == Q.S_ORDER} == {0, 1, 2}
     assert {o[3] for o in ops if o[0] == "sopt" and o[2] == Q.S_HEIGHT} == {1, 2, 3, 4, 5}
@@ -274,8 +356,10 @@ def test_named_conditions(traces, name):
 
 
 def test_conditions_can_fail():
-    """The checkers are not vacuous: a sequence of renders alone meets none."""
+    """The checkers are not vacuous: a sequence of renders and one composite
+    without the passes meets none."""
     ops = [("attach", 0, "s257"), ("attach", 1, "s33")] + [("render", ci, 0, 1, ("own",)) for ci in (0, 1, 0, 1)]
+    ops.append(("render", 1, 0, 2, ("over", "s33", 3)))
     exps = Q.trace(ops)
     assert not any(c(exps) for c in CONDITIONS.values())
     assert pairs(exps) == {("attach", "own/kd")}
@@ -300,6 +384,22 @@ def test_rejections_are_the_documented_ones():
     for key, bad in Q.OPT_BAD.items():
         assert not any(Q.opt_valid(key, v) for v in bad) and all(Q.opt_valid(key, v) for v in Q.OPT_VALUES[key])
     assert m.step(("tree", "s9", "bad_dup")).reject == "tree_dup" and m.tree["s9"] == "built"
+    # the deferred pass: kernel 2 and any flag but COUNT are RT_ERR_INVALID, unfilled own planes RT_ERR_STATE
+    x = lambda mode, flags, skip: m.step(("render", 0, mode, flags, ("xshadow", "s1", 0, skip, 0)))  # noqa: E731
+    assert x(Q.KD, 0, 0).reject == x(Q.KD, Q.COUNT, 1).reject == "xshadow_k2" and m.cams[0].mesh == "s9"
+    assert m.step(("shadow", 0, 0)).reject == "xshadow_k2"
+    m.step(("opt", 0, Q.K_KERNEL, 3))
+    assert m.step(("shadow", 0, 0)).reject == "shadow_unfilled"
+    for flags in (Q.HIT, Q.SHADOW, Q.AOV, Q.COUNT | Q.HIT):
+        assert x(Q.KD, flags, 0).reject == "xshadow_flags"
+    assert x(Q.KD, 64, 0).reject == "flags_high" and x(Q.FLAT, 0, 1).reject == "xshadow_flat"
+    m.step(("render", 0, Q.KD, Q.HIT | Q.AOV, ("own",)))
+    e = m.step(("shadow", 0, 0))
+    assert e.reject is None and e.layers[0][0][5] is True and m.cams[0].aov_filled
+    e = x(Q.KD, Q.COUNT, 1)
+    assert e.reject is None and e.xshadow == (1, 0) and m.cams[0].mesh == "s1"
+    assert [spec[5] for spec, _ in e.layers] == [True, True] and [b for _, b in e.layers] == [0, 9]
+    assert Q.REJECT_CODES == dict(xshadow_flat=-1, xshadow_k2=-1, xshadow_flags=-1, shadow_unfilled=-5)
 
 
 def test_hit_planes_are_the_numpy_restatements(oracle):
@@ -350,8 +450,9 @@ def test_model_is_self_consistent(oracle, traces, seed):
     """Every render's expectation from the caches equals the one computed
     with a fresh oracle scene for that step: a cache-key mistake shows here."""
     n = lit = 0
+    assert sum(1 for e in traces[seed] if _is_x(e) and e.op[1] == 0) <= Q.XSHADOW_CAM0_CAP   # the numpy reference's cost
     for i, e in enumerate(traces[seed]):
-        if not _is_frame(e):
+        if not (_is_frame(e) or (e.kind == "shadow" and not e.reject)):
             continue
         a, b = Q.expected(oracle, e), Q.expected(oracle, e, fresh=True)
         for x, y in zip(a, b):

@@ -608,3 +608,181 @@ def test_light_tie_entry_equals_lmax():
     assert int(c1[0]) - int(c0[0]) >= got[0]                 # every shadow ray visits the root
     assert int(c1[4]) - int(c0[4]) == got[2], (got, c0, c1)  # and descends only where maxt0 < Lmax
     assert got == (405, 48, 58, 299), got
+
+
+# ------------------------------------------- the deferred shadow pass (rt_shadow_over)
+# What tests/test_gpu_xshadow_synth.py's scenes hold, on the two oracles alone.
+
+def _np():
+    from oracle import np_oracle as N
+    from tests import test_xshadow_cpu as X
+    return N, X
+
+
+def _twin(sc, xf):
+    """The numpy reference of sc's object at xf under its twin: cross_shadow of
+    two objects of the same mesh, tree and transform, with each pass's
+    counters -> (argb, hit, planes, classes), [base's counters, twin's]."""
+    N, X = _np()
+    P, cam = S.np_scene(sc), sc.np_camera()
+    Xf = N.IDENT if xf is None else np.asarray(xf, F)
+    tr = X.trace_object(P, cam, Xf, np.arange(sc.w * sc.h))
+    cnt = [[0] * 5, [0] * 5]
+    return X.cross_shadow(P, cam, [Xf, Xf], traced=[tr, tr], cnt=cnt), cnt
+
+
+@pytest.mark.parametrize("name", list(S.TWIN_CASES))
+def test_twin_pass_walks_the_fused_corpus(name):
+    """A twin (the same mesh, tree and transform from a second camera, hit
+    base = the triangle count) owns no pixel of the composite (the depth test
+    is strict), so its pass walks exactly the hit points of the fused shadow
+    render, each as a foreign pixel: nothing excluded.  Its shadow set is the
+    self pass's, and both frames are the C oracle's shadow frame, with the
+    numpy reference as the judge.  Counters: the oracle's shadow render minus
+    its plain render is exact for both passes on [0], [1], [4] (the DFS does
+    not depend on the exclusion) and for the self pass on [2]; the twin's
+    accept events [2] are no fewer (it excludes nothing)."""
+    make, xfs = S.TWIN_CASES[name]
+    sc = make()
+    for xname, xf in xfs:
+        (argb, hit, _, cls), cnt = _twin(sc, xf)
+        assert (cls["owner"] != 1).all(), (name, xname)
+        assert (cls["by"][0] == cls["by"][1]).all(), (name, xname, np.flatnonzero(cls["by"][0] != cls["by"][1])[:5])
+        c0, c1 = sc.oracle(0, xform=xf)[2], sc.oracle(0, xform=xf, shadow=True)
+        assert (hit == c1[1]).all() and (argb == c1[0]).all(), (name, xname, np.flatnonzero(argb != c1[0])[:5])
+        diff = [int(c1[2][k]) - int(c0[k]) for k in range(5)]
+        assert [cnt[0][k] for k in (0, 1, 2, 4)] == [diff[k] for k in (0, 1, 2, 4)], (name, xname, cnt, diff)
+        assert [cnt[1][k] for k in (0, 1, 4)] == [diff[k] for k in (0, 1, 4)] and cnt[1][2] >= diff[2], (name, xname, cnt)
+        S.pass_check(argb, cnt[1], c1[0], diff, (name, xname))
+
+
+def test_xshadow_scale_exponents():
+    """scaled_soup(e)'s shadow frame has a shadowed pixel at 2^7 alone of
+    SCALE_EXPONENTS (1 of 128 hit pixels; 21 at 2^0, none from 2^-8 down: the
+    light stays 2 away from the eye on every axis while the scene shrinks)."""
+    got = {}
+    for e in S.SCALE_EXPONENTS:
+        m, sh = _shadowed(S.scaled_soup(e))
+        got[e] = int(sh.sum())
+    assert tuple(e for e in S.SCALE_EXPONENTS if got[e] > 0) == S.XSHADOW_SCALE_EXPONENTS, got
+    assert got[7] == 1
+
+
+@pytest.mark.parametrize("pose", S.LIGHT_POSE_NAMES)
+def test_xshadow_two_soups_classes(pose):
+    """soup(65) from light_scene(pose)'s eye under itself at the two offsets of
+    XSHADOW_OFFSETS: layer pixels shadowed by the base only, by both, base
+    pixels shadowed by the layer only, by both (XSHADOW_CLASSES).  Every class
+    holds at least 2 pixels at every pose and offset but "inside", whose light
+    shadows nothing (the control)."""
+    _, X = _np()
+    for k in range(len(S.XSHADOW_OFFSETS)):
+        got = X.class_counts(X.pair_want(pose, k)[0][3])
+        assert (min(got) >= 2) if pose != "inside" else (got == (0, 0, 0, 0)), (pose, k, got)
+        assert got == S.XSHADOW_CLASSES[pose, k], (pose, k, got)
+
+
+def test_xshadow_tiny_occluders():
+    """soup(n) at XSHADOW_TINY_OFFSET over soup(65), and soup(65) at that
+    offset over soup(n), from the default camera: the small soup as the layer
+    shadows a base pixel at every n (n = 1, a leaf root: 2 pixels)."""
+    _, X = _np()
+    for n in S.SOUP_NS:
+        over, under = (X.class_counts(X.tiny_want(n, layer)[0][3]) for layer in (True, False))
+        assert over[2] + over[3] >= 1, (n, over)
+        assert (over, under) == S.XSHADOW_TINY[n], (n, over, under)
+    assert S.XSHADOW_TINY[1][0][2] + S.XSHADOW_TINY[1][0][3] == 2
+
+
+def _foreign_segments(want, Ps, traced, B):
+    """Pass B's foreign pixels (hit, not B's own) and their segment classes."""
+    hit, owner = want[1], want[3]["owner"]
+    idx = np.flatnonzero((hit >= 0) & (owner != B))
+    d = want[2][0].view(F)[idx]
+    return idx, S.segment_classes(Ps[B], d, [traced[B][3][int(j)] for j in idx])
+
+
+def test_xshadow_segments_end_before_inside_and_beyond_the_box():
+    """The foreign pixels of the two-soup scenes by where their shadow segment
+    ends relative to the occluder's root box: before it (root entry at or
+    beyond Lmax: no descent), inside it, beyond it.  Each class occurs over
+    the poses; a pixel of the first class is never shadowed."""
+    total = np.zeros(3, np.int64)
+    for pose in S.LIGHT_POSE_NAMES:
+        _, X = _np()
+        want, Ps, traced = X.pair_want(pose, 0)
+        for B in (0, 1):
+            idx, cls = _foreign_segments(want, Ps, traced, B)
+            total += np.bincount(cls[cls >= 0], minlength=3)
+            assert not want[3]["by"][B][idx[cls == 0]].any(), (pose, B)
+    print("segments ending before / inside / beyond the occluder's root box:", total)
+    assert (total >= 1).all(), total
+
+
+def _faulty_pass(want, Ps, traced, B, scale=None, le=False, exclude_foreign=False):
+    """Object B's pass over the composite `want` (cross_shadow's result)
+    restated with one fault of a wrong kernel: scale, the Lmax factor; le, a
+    box entered where maxt0 <= Lmax; exclude_foreign, the own-triangle
+    exclusion applied to a foreign pixel (its owner's triangle index read as
+    one of B's).  -> (argb, counters)."""
+    N, _ = _np()
+    scale = N.SHADOW_SCALE if scale is None else F(scale)
+    argb, hit, owner = want[0].copy(), want[1], want[3]["owner"]
+    bases = np.concatenate([[0], np.cumsum([len(p["e1"]) for p in Ps])])
+    d0 = want[2][0].view(F)
+    cnt = [0] * 5
+    argb[want[3]["by"].any(0)] = 1       # (the other passes' shadows are not this pass's business)
+    with np.errstate(all="ignore"):
+        for j in np.flatnonzero(hit >= 0):
+            rmi = int(hit[j] - bases[owner[j]]) if owner[j] == B or exclude_foreign else -1
+            r, od = traced[B][3][j]
+            sv = [F(F(F(d0[j] * r[k]) - od[k]) - F(2)) for k in range(3)]
+            L2 = F(F(F(sv[0] * sv[0]) + F(sv[1] * sv[1])) + F(sv[2] * sv[2]))
+            lmax = F(F(np.sqrt(np.float64(L2))) * scale)
+            occ = [False]
+
+            def leaf(t, u, v, w):
+                if t != rmi and N._mt_accept(u, v, w, lmax):
+                    cnt[2] += 1
+                    occ[0] = True
+
+            N._walk(Ps[B], list(N.dev_normalize(*sv)), (F(-2), F(-2), F(-2)), leaf,
+                    lim=np.nextafter(lmax, F(np.inf)) if le else lmax, cnt=cnt)
+            if occ[0]:
+                argb[j] = 0
+    return argb, cnt
+
+
+def test_a_wrong_kernel_fails_the_comparison():
+    """Three faults a pass could have, restated in numpy and fed to the
+    comparison the GPU tests use (synth.pass_check): each is caught by a scene,
+    and the faultless restatement passes it.
+      the Lmax factor 1 instead of 1 - 2^-10: a twin pass finds each hit
+        point's own triangle (soup(33): frame);
+      the own-triangle exclusion applied to foreign pixels: the two soups of
+        "pnp" (frame);
+      a box entered at maxt0 <= Lmax: light_tie(), whose frame is the same and
+        whose descents are 106 instead of 58."""
+    N, X = _np()
+
+    def one(want, Ps, traced, B, **fault):
+        ok = _faulty_pass(want, Ps, traced, B)
+        assert (ok[0] == 0).sum() == want[3]["by"][B].sum()
+        bad = _faulty_pass(want, Ps, traced, B, **fault)
+        S.pass_check(ok[0], ok[1], ok[0], ok[1])
+        with pytest.raises(AssertionError):
+            S.pass_check(bad[0], bad[1], ok[0], ok[1])
+        return ok, bad
+
+    def twin(sc):
+        P, cam = S.np_scene(sc), sc.np_camera()
+        tr = X.trace_object(P, cam, N.IDENT, np.arange(sc.w * sc.h))
+        return X.cross_shadow(P, cam, [N.IDENT, N.IDENT], traced=[tr, tr]), [P, P], [tr, tr]
+
+    ok, bad = one(*twin(S.soup_scene(33)), 1, scale=1.0)
+    assert (bad[0] != ok[0]).sum() >= 20
+    ok, bad = one(*X.pair_want("pnp", 0), 0, exclude_foreign=True)
+    assert (bad[0] != ok[0]).any()
+    sc = S.SynthScene(*S.light_tie(), S.W, S.H_, cam_kw=S.THRESHOLD_CAM)
+    ok, bad = one(*twin(sc), 1, le=True)
+    assert (bad[0] == ok[0]).all() and (ok[1][4], bad[1][4]) == (58, 106)

@@ -53,7 +53,7 @@ def trace_object(S, cam, X, pixels, rad=None):
     return argb, hit, planes, rays
 
 
-def cross_shadow(S, cam, xforms, pixels=None, order=None, depth=None, traced=None):
+def cross_shadow(S, cam, xforms, pixels=None, order=None, depth=None, traced=None, cnt=None, own_cnt=None):
     """The composite of one object per transform in `xforms` with every
     object's shadows applied, at the pixel indices `pixels` (all by default).
 
@@ -68,6 +68,10 @@ def cross_shadow(S, cam, xforms, pixels=None, order=None, depth=None, traced=Non
     order: the objects' passes in that order (the result does not depend on
     it).  depth: {position in pixels: float} replaces plane 0's value for the
     test.  traced: the objects' trace_object results, when the caller has them.
+    cnt: one list of five counters per object; object B's pass adds its shadow
+    walks' visits (trace_shadow's cnt) to cnt[B], over every pixel it tests;
+    with own_cnt (the same shape) the walks of B's own pixels go to own_cnt[B]
+    instead (a skip_own pass walks the others alone).
     -> (argb u32 [m], hit i64 [m], planes u32 bits [10, m], classes) with
     classes = {"owner": i64 [m] (-1: a miss), "by": bool [nobj, m]}."""
     Ss = S if isinstance(S, list) else [S] * len(xforms)
@@ -89,7 +93,8 @@ def cross_shadow(S, cam, xforms, pixels=None, order=None, depth=None, traced=Non
             for j in np.nonzero(hit >= 0)[0]:
                 d = d0[j] if depth is None or int(j) not in depth else F(depth[int(j)])
                 rmi = int(hit[j] - bases[B]) if owner[j] == B else -1
-                by[B, j] = N.trace_shadow(Ss[B], rmi, d, traced[B][3][j])
+                c = cnt if own_cnt is None or owner[j] != B else own_cnt
+                by[B, j] = N.trace_shadow(Ss[B], rmi, d, traced[B][3][j], cnt=None if c is None else c[B])
             argb[by[B]] = 0
     return argb, hit, planes, {"owner": owner, "by": by}
 
@@ -100,6 +105,52 @@ def class_counts(classes):
     o, by = classes["owner"], classes["by"]
     return (int(((o == 1) & by[0] & ~by[1]).sum()), int(((o == 1) & by[0] & by[1]).sum()),
             int(((o == 0) & by[1] & ~by[0]).sum()), int(((o == 0) & by[1] & by[0]).sum()))
+
+
+# ------------------------------------------- the synthetic scenes' two-object frames
+# (tables in tests/synth.py, conditions in tests/test_synth_cpu.py, the kernels in
+# tests/test_gpu_xshadow_synth.py)
+
+def _frozen(out):
+    for a in out[:3]:
+        a.setflags(write=False)
+    return out
+
+
+def two_objects(scs, cam, X, flat_base=False):
+    """cross_shadow of scs[0]'s mesh at the identity and scs[1]'s at X from the
+    numpy camera cam -> (want, prepared scenes, traced).  flat_base: the base
+    layer is the flat list's render (the C oracle's frame and hit index, the
+    planes by seq.hit_planes' flat arithmetic): the depths the passes read are
+    then the flat walk's."""
+    Ps = [N.prepare(sc.pts, N.nodes_from_array(sc.onodes), cam) for sc in scs]
+    px = np.arange(cam["w"] * cam["h"])
+    traced = [trace_object(Ps[0], cam, N.IDENT, px), trace_object(Ps[1], cam, X, px)]
+    if flat_base:
+        from tests import seq as Q
+        argb, hit, _ = scs[0].oracle(1)
+        rays = np.array([N.primary_ray(cam, i % cam["w"], i // cam["w"]) for i in px], F)
+        planes = Q.hit_planes(Ps[0], rays, N.IDENT, Q.FLAT, hit, N.RAD).view(F)
+        traced[0] = (argb, hit, planes, traced[0][3])
+    return _frozen(cross_shadow(Ps, cam, [N.IDENT, X], traced=traced)), Ps, traced
+
+
+@functools.lru_cache(None)
+def pair_want(pose, k, flat_base=False):
+    """The two soups of synth.XSHADOW_CLASSES[pose, k]: light_scene(pose) at the
+    identity under itself at the offset XSHADOW_OFFSETS[k]."""
+    from tests import synth as SY
+    with SY.light_scene(pose) as sc:
+        return two_objects([sc, sc], sc.np_camera(), offset_xform(*SY.XSHADOW_OFFSETS[k]), flat_base)
+
+
+@functools.lru_cache(None)
+def tiny_want(n, small_is_layer):
+    """soup(n) over (small_is_layer) or under soup(65) of synth.XSHADOW_TINY."""
+    from tests import synth as SY
+    with SY.soup_scene(n) as small, SY.soup_scene(SY.LIGHT_N) as big:
+        scs = [big, small] if small_is_layer else [small, big]
+        return two_objects(scs, big.np_camera(), offset_xform(*SY.XSHADOW_TINY_OFFSET))
 
 
 # ------------------------------------------------------------ the dump 40x24 cases
