@@ -397,6 +397,11 @@ def grid_poses(w, h):
             ("split", grid_eye_on_split(w, h), None))
 
 
+#: RT_OPT_FAST_USED after a kernel-3 render of a soup of two or more triangles,
+#: or of soup(33)'s built tree, at the "xlate" setting (and at "rot"): bit 0, the
+#: frame proved the float walks, and bit 2, under an object transform
+XLATE_FAST_USED = 5
+
 #: the object transforms the hand-made trees render under beside the identity
 TREE_XFS = (("rot", rot_y(17.0)), ("xlate", rot_y(0.0, (0.01, -0.005, 0.02))))
 
@@ -761,6 +766,263 @@ def segment_classes(P, d, rays):
                 continue
             out[j] = 0 if not maxt0 < lmax else (1 if lmax <= mint1 else 2)
     return out
+
+
+# ------------------------------------------- translated walks on exact split values
+# An object offset moves the nearest-hit walk onto forms of their own
+# (rt_kernels_impl.h xfast_slot, two_level_fast<kXl>, visit_item<kTranslated>):
+# the split value is computed per visit, s = s2 + ds, a lane whose |s| is below
+# 2^-20 leaves the float compare, and maxt0 * dir == s / mint1 * dir == s are
+# decided by pred::lt_eps_x / gt_eps_x (true below |s| = 1, false from there,
+# but for s == -1 / s == +1).  The cases below carry split planes of grid()'s
+# tree onto those values with exact float32 offsets; tests/test_synth_cpu.py
+# counts the visits of each class on the oracle, tests/test_gpu_synth.py renders
+# them.
+
+XL_SMALL = F(2.0) ** F(-20)                      # pred::kSmall, the guard of the float compares
+XL_BELOW = np.nextafter(XL_SMALL, F(0))          # the largest float below it
+#: the classes of an interior visit that orders its children (xl_classes)
+XL_CLASSES = ("s0x", "s0y", "s0z",               # s == 0, by the axis of the cut
+              "tiny+", "tiny-",                  # 0 < |s| < 2^-20 (the double forms' lanes), by the sign of s
+              "below+", "below-",                # of those, |s| one ulp below 2^-20
+              "guard+", "guard-",                # |s| == 2^-20: the first value of the float compares
+              "lt_eq<1", "gt_eq<1",              # maxt0 * dir == s / mint1 * dir == s, 2^-20 <= |s| < 1: true
+              "lt_eq>1", "gt_eq>1",              # the same with |s| > 1: false
+              "lt_-1", "gt_-1", "lt_+1", "gt_+1",  # the same at s == -1 (lt true, gt false) and s == +1 (lt false, gt true)
+              "s1_eps")                          # fl(s1 + 1e-16 + ds) in double is not the float sum fl(s1 + ds)
+#: the walk's forms xl_walk restates: the reference's doubles, the kernels'
+#: float forms, and five plausible wrong kernels
+XL_FAULTS = ("tiny_float",                       # (a) the tiny lanes keep the float compare
+             "lt_no_eq",                         # (b) lt_eps_x without its equality term
+             "eq_any",                           # (c) equality accepted for |s| >= 1 as well
+             "pm1_swapped",                      # (d) the s == -1 / s == +1 exceptions swapped between lt and gt
+             "s1_plain")                         # (e) s1 as fl(s1 + ds), without the 1e-16
+XL_FORMS = ("ref", "float") + XL_FAULTS
+
+
+def xl_walk(P, r, od, on_leaf, lim=None, cnt=None, form="ref", classes=None):
+    """np_oracle._walk restated with the child ordering in one of XL_FORMS
+    ("ref" is _walk itself, term for term; "float" is xfast_slot's: lt_eps_x /
+    gt_eps_x on s = fl(s2 + ds) unless |s| < 2^-20 or NaN, the double forms
+    there, s1 the double expression).  classes: a dict the walk adds each
+    ordering visit's XL_CLASSES to."""
+    D, EPS = N.D, N.EPS
+    inv = [F(F(1) / r[k]) for k in range(3)]
+    o = [F(od[k] / r[k]) for k in range(3)]
+    stack = [0]
+    while stack:
+        vx = P["vox"][stack.pop()]
+        if vx["leaf"]:
+            if cnt is not None:
+                cnt[1] += 1
+            t = vx["tri"]
+            e1, e2, dt = P["e1"][t], P["e2"][t], P["dt"][t]
+            p = N.cross(r, e2)
+            f = N.dot(p, e1)
+            if not (D(f) < EPS and D(f) > -EPS):
+                pe1 = F(D(1.0) / D(f))
+                tt = [F(dt[k] - od[k]) for k in range(3)]
+                q = N.cross(tt, e1)
+                on_leaf(t, F(pe1 * N.dot(p, tt)), F(pe1 * N.dot(r, q)), F(pe1 * N.dot(e2, q)))
+            continue
+        if cnt is not None:
+            cnt[0] += 1
+        bo, cf = vx["bo"], vx["cf"]
+        t0 = [F(bo[k] * inv[k]) if r[k] > 0 else F(bo[k + 3] * inv[k]) for k in range(3)]
+        t1 = [F(bo[k + 3] * inv[k]) if r[k] > 0 else F(bo[k] * inv[k]) for k in range(3)]
+        dr = F(F(F(r[0] * cf[0]) + F(r[1] * cf[1])) + F(r[2] * cf[2]))
+        ds = F(F(F(od[0] * cf[0]) + F(od[1] * cf[1])) + F(od[2] * cf[2]))
+        maxt0 = np.fmax(F(t0[2] + o[2]), np.fmax(F(t0[0] + o[0]), F(t0[1] + o[1])))
+        mint1 = np.fmin(F(t1[2] + o[2]), np.fmin(F(t1[0] + o[0]), F(t1[1] + o[1])))
+        if not (D(mint1) >= D(maxt0) - EPS and D(maxt0) > -EPS and (lim is None or maxt0 < lim)):
+            continue
+        if cnt is not None:
+            cnt[4] += 1
+        mx, mn = F(maxt0 * dr), F(mint1 * dr)
+        s = F(vx["s2"] + ds)
+        s1 = F(D(vx["s1"]) + EPS + D(ds))
+        tiny = not abs(s) >= XL_SMALL
+        if classes is not None:
+            sign = "+" if s > 0 else "-"
+            found = ["s0" + "xyz"[[float(c) for c in cf].index(1.0)]] if s == 0 else ["tiny" + sign] if tiny else ["guard" + sign] if abs(s) == XL_SMALL else []
+            if abs(s) == XL_BELOW:
+                found.append("below" + sign)
+            if not tiny:
+                size = "eq<1" if abs(s) < 1 else "eq>1" if abs(s) > 1 else "-1" if s < 0 else "+1"
+                found += ["lt_" + size] * bool(mx == s) + ["gt_" + size] * bool(mn == s)
+            if s1 != F(vx["s1"] + ds):
+                found.append("s1_eps")
+            for c in found:
+                classes[c] = classes.get(c, 0) + 1
+        if form == "ref" or (tiny and form != "tiny_float"):
+            lf, pa = bool(D(mx) < D(s) + EPS), bool(D(mn) > D(s) - EPS)
+        else:
+            below1 = bool(abs(s) < 1)
+            lt_eq = dict(lt_no_eq=False, eq_any=True, pm1_swapped=below1 or s == 1).get(form, below1 or s == -1)
+            gt_eq = dict(eq_any=True, pm1_swapped=below1 or s == -1).get(form, below1 or s == 1)
+            lf, pa = bool(mx < s or (mx == s and lt_eq)), bool(mn > s or (mn == s and gt_eq))
+        if form == "s1_plain":
+            s1 = F(vx["s1"] + ds)
+        if lf:
+            if pa:
+                stack.append(vx["right"])
+            stack.append(vx["left"])
+        else:
+            if mn < s1 or mx < s1:
+                stack.append(vx["left"])
+            stack.append(vx["right"])
+
+
+def xl_render(sc, xform, form="ref", classes=None):
+    """The numpy restatement's KD render of sc with xl_walk in `form` as its
+    walk -> (argb, hit, counters[5])."""
+    import functools
+    walk = N._walk
+    N._walk = functools.partial(xl_walk, form=form, classes=classes)
+    try:
+        return sc.oracle_np(0, xform=xform)
+    finally:
+        N._walk = walk
+
+
+def xl_classes(sc, xform):
+    """The ordering visits of sc's frame under xform by class -> a tuple in
+    the order of XL_CLASSES.  The walk that counts them visits as many interior
+    nodes and descends as often as the C oracle, and renders its frame."""
+    classes = {}
+    argb, hit, cnt = xl_render(sc, xform, "ref", classes)
+    want = sc.oracle(0, xform=xform)
+    assert (int(cnt[0]), int(cnt[4])) == (int(want[2][0]), int(want[2][4])), (cnt, want[2])
+    assert (hit == want[1]).all() and (argb == want[0]).all()
+    assert set(classes) <= set(XL_CLASSES), classes
+    return tuple(classes.get(c, 0) for c in XL_CLASSES)
+
+
+def xl_offset(t, rot=None):
+    """A 12-float transform of the rotation rows `rot` (a 12-float transform
+    whose offsets are dropped; None: the identity) and the offset t."""
+    x = np.array(N.IDENT if rot is None else rot, F).reshape(3, 4).copy()
+    x[:, 3] = [F(c) for c in t]
+    return x.reshape(12)
+
+
+def xl_grid(e, w=W, h=H_, **opts):
+    """grid() and the default camera times 2^e (scaled()) at w x h."""
+    v, kw = scaled(grid()[0], default_cam(w, h), e)
+    return SynthScene(v, grid()[1], w, h, cam_kw=kw, **opts)
+
+
+#: a rotation by 2^-60 about the view axis as float32 gives it (cos = 1, sin =
+#: 2^-60): the rays of the frame's centre column and row, whose x or y is an
+#: exact zero at the identity, get components of the size of 2^-60 of either
+#: sign instead, so that maxt0 * dir and mint1 * dir lie within 1e-16 of a
+#: split value of zero without being equal to it.  No other scene tells the
+#: double forms of the tiny lanes from the float compares (fault (a)).
+XL_TURN = np.array([1, -F(2.0) ** F(-60), 0, 0, F(2.0) ** F(-60), 1, 0, 0, 0, 0, 1, 0], F)
+
+
+def _xl_cases():
+    """-> {name: (scale exponent, transform, the classes the case is in the
+    table for, whether the frame proves the translated float walk:
+    RT_OPT_FAST_USED & 4 as the library reports it)}.  The offsets are sums and
+    differences of float32 values that are exact.  Relative to the eye grid()'s
+    tree has x splits (s2) at 0, +-0.15, -0.2 and -0.3 and y splits at 0 alone,
+    with one s1 at y07 = 0.17 - 0.1 (test_synth_cpu.py finds them in the built
+    tree).  So an x offset of -0.15 has split values of exactly zero on x and
+    on y at once; a y offset takes the y splits off the eye, and -y07 puts that
+    s1 plane on it (no y offset can carry a y s2 onto the eye: they are all
+    there already); an x offset of g alone leaves s = g at the x = 0 splits.
+    Under SIGNED_PERM the rays travel along the object's +x: the offsets put
+    the grid in front of them."""
+    x15, y07, g21 = F(0.15), F(F(0.17) - F(0.1)), F(2.0) ** F(-21)
+    z0 = F(F(-0.6) - F(-1.0))                     # the root box's near face relative to the eye
+    on_eye = ("s0x", "lt_eq<1", "gt_eq<1", "s1_eps")
+    t = {}
+    # a split plane onto the eye, s == 0 (and, beside it, ties below 1): on x and
+    # y at once; on x with the y splits off the eye (and the s1 plane y07 on it:
+    # s1 + 1e-16 + ds = 1e-16); that s1 plane with the x = 0 splits alone.
+    # ("eighth" below has exact zeros on y alone.)
+    t["x_on_eye"] = (0, xl_offset((-x15, 0, 0)), on_eye + ("s0y",), True)
+    t["x_on_eye_y_off"] = (0, xl_offset((-x15, -y07, 0)), on_eye, True)
+    t["y_s1_on_eye"] = (0, xl_offset((0, -y07, 0)), ("s0x", "gt_eq<1", "s1_eps"), True)
+    # either side of the guard |s| < 2^-20, of either sign
+    t["tiny+"] = (0, xl_offset((F(-x15 + g21), 0, 0)), ("tiny+",), True)
+    t["tiny-"] = (0, xl_offset((F(-x15 - g21), 0, 0)), ("tiny-",), True)
+    t["guard+"] = (0, xl_offset((F(-x15 + XL_SMALL), 0, 0)), ("guard+",), True)
+    t["guard-"] = (0, xl_offset((F(-x15 - XL_SMALL), 0, 0)), ("guard-",), True)
+    t["below+"] = (0, xl_offset((XL_BELOW, 0, 0)), ("tiny+", "below+"), True)
+    t["below-"] = (0, xl_offset((-XL_BELOW, 0, 0)), ("tiny-", "below-"), True)
+    t["tiny_y+"] = (0, xl_offset((0, g21, 0)), ("tiny+",), True)
+    # ties below 1, and above it on the x8 grid
+    t["eighth"] = (0, xl_offset((0.125, 0, 0)), ("s0y", "lt_eq<1", "gt_eq<1"), True)
+    t["x8_split"] = (3, xl_offset((F(x15 * F(8)), 0, 0)), ("lt_eq>1", "gt_eq>1"), True)
+    t["x8_+1"] = (3, xl_offset((1, 0, 0)), ("lt_+1", "gt_+1", "gt_eq>1"), True)
+    t["x8_-1"] = (3, xl_offset((-1, 0, 0)), ("lt_-1", "gt_-1", "gt_eq>1"), True)
+    # s == -1 and s == +1 exactly
+    t["x4_-1"] = (2, xl_offset((-1, 0, 0)), ("lt_-1", "gt_-1"), True)
+    t["x4_+1"] = (2, xl_offset((1, 0, 0)), ("lt_+1", "gt_+1"), True)
+    # toward the eye: the root box's near face 2^-18 in front of it (the proof's
+    # margin is 2^-19 + 2^-22 (M + |od|)), 2^-20 (refused: the double forms), 0.15
+    t["z_margin"] = (0, xl_offset((-x15, 0, F(-z0 + F(2.0) ** F(-18)))), ("s0x", "s0y", "gt_eq<1", "s1_eps"), True)
+    t["z_refused"] = (0, xl_offset((-x15, 0, F(-z0 + XL_SMALL))), ("s0x", "s0y", "gt_eq<1", "s1_eps"), False)
+    t["z_quarter"] = (0, xl_offset((-x15, 0, -0.25)), on_eye, True)
+    # a rotation as well: the offset's component reaches the walk as a per-ray field
+    t["turn_x_on_eye"] = (0, xl_offset((-x15, 0, 0), XL_TURN), on_eye, True)
+    t["perm_z_x_on_eye"] = (0, xl_offset((-x15, 0, 0), PERM_Z), on_eye, True)
+    t["perm_z_x_on_eye_y_off"] = (0, xl_offset((-x15, -y07, 0), PERM_Z), on_eye, True)
+    t["perm_z_tiny+"] = (0, xl_offset((F(-x15 + g21), 0, 0), PERM_Z), ("tiny+",), True)
+    t["perm_z_eighth"] = (0, xl_offset((0.125, 0, 0), PERM_Z), ("lt_eq<1", "gt_eq<1"), True)
+    t["perm_z_x8_split"] = (3, xl_offset((F(x15 * F(8)), 0, 0), PERM_Z), ("lt_eq>1", "gt_eq>1"), True)
+    t["perm_z_x8_+1"] = (3, xl_offset((1, 0, 0), PERM_Z), ("lt_+1", "gt_+1"), True)
+    t["perm_z_x8_-1"] = (3, xl_offset((-1, 0, 0), PERM_Z), ("lt_-1", "gt_-1"), True)
+    t["perm_+1"] = (0, xl_offset((1, 0, -1), SIGNED_PERM), ("s0y", "s0z", "lt_+1", "gt_+1", "lt_eq<1"), True)
+    t["perm_tiny+"] = (0, xl_offset((1, g21, -1), SIGNED_PERM), ("tiny+",), True)
+    t["perm_ties"] = (0, xl_offset((0.5, -y07, -0.7), SIGNED_PERM), ("lt_eq<1", "gt_eq<1"), True)
+    t["perm_x4"] = (2, xl_offset((3, 0, -3), SIGNED_PERM), ("s0y", "lt_eq>1", "gt_eq>1", "gt_+1"), True)
+    return t
+
+
+XL_CASES = _xl_cases()
+#: the cases whose split values are exact zeros also render GRID_FRAMES' other frames
+XL_ALL_FRAMES = tuple(name for name, c in XL_CASES.items() if any(k.startswith("s0") for k in c[2]))
+#: name -> the visits of the case's 33x19 frame by class, in the order of XL_CLASSES
+#: (xl_classes; test_synth_cpu.py)
+XL_COUNTS = {
+    "x_on_eye": (372, 190, 0, 0, 0, 0, 0, 0, 0, 70, 70, 0, 0, 0, 0, 0, 627, 595),
+    "x_on_eye_y_off": (350, 0, 0, 0, 0, 0, 0, 0, 0, 58, 58, 0, 0, 0, 0, 0, 622, 505),
+    "y_s1_on_eye": (513, 0, 0, 0, 0, 0, 0, 0, 0, 0, 50, 0, 0, 0, 0, 0, 696, 961),
+    "tiny+": (0, 190, 0, 372, 0, 0, 0, 0, 0, 73, 73, 0, 0, 0, 0, 0, 627, 133),
+    "tiny-": (0, 184, 0, 0, 372, 0, 0, 0, 0, 69, 69, 0, 0, 0, 0, 0, 627, 127),
+    "guard+": (0, 190, 0, 0, 0, 0, 0, 372, 0, 73, 73, 0, 0, 0, 0, 0, 627, 133),
+    "guard-": (0, 184, 0, 0, 0, 0, 0, 0, 372, 71, 71, 0, 0, 0, 0, 0, 627, 127),
+    "below+": (0, 219, 0, 530, 0, 530, 0, 0, 0, 0, 46, 0, 0, 0, 0, 0, 711, 163),
+    "below-": (0, 213, 0, 0, 522, 0, 522, 0, 0, 0, 48, 0, 0, 0, 0, 0, 711, 163),
+    "tiny_y+": (517, 0, 0, 228, 0, 0, 0, 0, 0, 0, 61, 0, 0, 0, 0, 0, 693, 1098),
+    "eighth": (0, 212, 0, 0, 0, 0, 0, 0, 0, 47, 73, 0, 0, 0, 0, 0, 621, 180),
+    "x8_split": (0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 10, 70, 662, 0, 0, 0, 0, 0),
+    "x8_+1": (0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 26, 0, 621, 0, 0, 47, 47, 0),
+    "x8_-1": (0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 650, 54, 54, 0, 0, 0),
+    "x4_-1": (0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 519, 36, 36, 0, 0, 0),
+    "x4_+1": (0, 0, 0, 0, 0, 0, 0, 0, 0, 16, 0, 0, 477, 0, 0, 35, 35, 0),
+    "z_margin": (850, 272, 0, 0, 0, 0, 0, 0, 0, 0, 735, 0, 0, 0, 0, 0, 0, 1151),
+    "z_refused": (820, 263, 0, 0, 0, 0, 0, 0, 0, 0, 668, 0, 0, 0, 0, 0, 0, 1124),
+    "z_quarter": (620, 261, 0, 0, 0, 0, 0, 0, 0, 87, 753, 0, 0, 0, 0, 0, 0, 926),
+    "turn_x_on_eye": (348, 189, 0, 0, 0, 0, 0, 0, 0, 70, 70, 0, 0, 0, 0, 0, 648, 585),
+    "perm_z_x_on_eye": (378, 105, 0, 0, 0, 0, 0, 0, 0, 12, 12, 0, 0, 0, 0, 0, 457, 476),
+    "perm_z_x_on_eye_y_off": (380, 0, 0, 0, 0, 0, 0, 0, 0, 12, 12, 0, 0, 0, 0, 0, 450, 415),
+    "perm_z_tiny+": (0, 105, 0, 378, 0, 0, 0, 0, 0, 13, 13, 0, 0, 0, 0, 0, 457, 79),
+    "perm_z_eighth": (0, 190, 0, 0, 0, 0, 0, 0, 0, 38, 58, 0, 0, 0, 0, 0, 449, 154),
+    "perm_z_x8_split": (0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 10, 13, 433, 0, 0, 0, 0, 0),
+    "perm_z_x8_+1": (0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 20, 0, 449, 0, 0, 38, 38, 0),
+    "perm_z_x8_-1": (0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 486, 38, 38, 0, 0, 0),
+    "perm_+1": (0, 46, 833, 0, 0, 0, 0, 0, 0, 80, 0, 0, 0, 0, 0, 62, 62, 35),
+    "perm_tiny+": (0, 0, 782, 42, 0, 0, 0, 0, 0, 70, 0, 0, 0, 0, 0, 56, 56, 0),
+    "perm_ties": (0, 0, 0, 0, 0, 0, 0, 0, 0, 384, 230, 0, 0, 0, 0, 0, 0, 0),
+    "perm_x4": (0, 51, 0, 0, 0, 0, 0, 0, 0, 0, 0, 385, 187, 0, 0, 0, 60, 33),
+}
+#: a case per fault of XL_FAULTS whose frame, hit buffer or counters the fault changes
+XL_CATCHES = dict(tiny_float="turn_x_on_eye", lt_no_eq="x_on_eye", eq_any="x8_split", pm1_swapped="x4_-1",
+                  s1_plain="y_s1_on_eye")
 
 
 def pass_check(got_argb, got_cnt, want_argb, want_cnt, what=""):

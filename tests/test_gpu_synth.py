@@ -9,8 +9,9 @@ box bounds of exactly zero (0 * inf = NaN in the slab products), leaf
 arithmetic at the reference's 1e-16 thresholds, trees that raise
 kCamUnordered, degenerate triangles in the KD leaf test, a light in every
 octant of the mesh, astride it and in the planes of its walls (the shadow
-walk's nine instances and its per-wave fall-back), and a radiance of its own
-per triangle.
+walk's nine instances and its per-wave fall-back), a radiance of its own
+per triangle, and object offsets that land split planes on exact zeros, on
+either side of the translated walks' 2^-20 guard and on exact ties.
 tests/test_synth_cpu.py proves on the oracle alone that each scene has the
 property it is here for, and anchors the oracle's values to the numpy
 restatement.  The frames are 33x19 and each scene keeps one camera whose
@@ -75,9 +76,13 @@ def test_tiny_trees(n):
                 _kd(sc, want, kernel, xf, what=what)
                 if n == 1:
                     assert sc.get_option(_lib.RT_OPT_FAST_USED) == 0, what
+                elif kernel == 3 and name == "xlate":  # the frame proves the translated float walk (bits 0 and 2)
+                    assert sc.get_option(_lib.RT_OPT_FAST_USED) == S.XLATE_FAST_USED, what
                 _flat(sc, want_flat, xf, what=what)
                 if kernel == 3:
                     _kd(sc, want_shadow, 3, xf, shadow=True, what=what + " shadow")
+                    if n > 1 and name == "xlate":      # and the light the shadow walk's (bit 1)
+                        assert sc.get_option(_lib.RT_OPT_FAST_USED) == S.XLATE_FAST_USED | 2, what
             assert sc.trixel.get_option(_lib.RT_SCENE_TWO_LEVEL_DEPTH) == S.TWO_LEVEL_DEPTH[n]
             if n >= 4:
                 assert S.TWO_LEVEL_DEPTH[n] == int(np.floor(np.log2(n))) - 2
@@ -251,6 +256,68 @@ def test_zero_components_and_zero_bounds(w, h, pose):
     _grid_case(w, h, name, kw, xf)
 
 
+# ------------------------------- translated walks on exact split values
+
+def _xl_params():
+    """Each case of XL_CASES at 33x19, the cases with exact zeros at
+    GRID_FRAMES' other frames as well: one live camera per parameter."""
+    out = [(name, S.W, S.H_) for name in S.XL_CASES]
+    out += [(name, w, h) for name in S.XL_ALL_FRAMES for w, h in S.GRID_FRAMES[1:]]
+    return out
+
+
+@pytest.mark.parametrize("name,w,h", _xl_params(), ids=lambda v: str(v))
+def test_translated_walks_on_exact_splits(name, w, h):
+    """grid() under the offsets of synth.XL_CASES, which carry split planes of
+    its tree onto the values where the translated walks change their form: s =
+    s2 + ds of exactly zero, either side of the 2^-20 guard of the float
+    compares, maxt0 * dir == s and mint1 * dir == s below and above |s| = 1
+    and at s == -1 and s == +1, s1 + 1e-16 + ds where the 1e-16 tells, alone
+    and with a rotation (tests/test_synth_cpu.py counts the visits of each
+    class per case and shows that five plausible wrong kernels fail this
+    comparison).  Every kernel configuration; on kernel 3 every unit width in
+    the float forms (xfast_slot, two_level_fast<kXl>), the one-level walk
+    (debug 1024) and the double forms (debug 2048: visit_item<kTranslated>,
+    two_level_iter<kTranslated>), items per lane 1, 2 and 96, a pool of 89,
+    the coarse table, and shadow rays: frame, hit buffer and counters are the
+    oracle's.  RT_OPT_FAST_USED & 4 is as the table records it per case."""
+    from cpp_cuda_raytracer_dev_amd import _lib
+    e, xf, _, fast = S.XL_CASES[name]
+    sc = S.xl_grid(e, w, h)
+    try:
+        want = {sh: sc.oracle(0, xform=xf, shadow=sh) for sh in (False, True)}
+        for kernel, order, rays in KERNELS:
+            sc.options(kernel=kernel, tile_order=order, rays=rays, coarse=8, debug=0, items=2, pool_cap=640)
+            what = f"xl {name} {w}x{h} k{kernel} o{order} r{rays}"
+            _kd(sc, want[False], kernel, xf, what=what)
+            if kernel == 3:
+                used = sc.get_option(_lib.RT_OPT_FAST_USED)
+                assert bool(used & 4) == fast and bool(used & 1) == fast, (what, used)
+                _kd(sc, want[True], 3, xf, shadow=True, what=what + " shadow")
+        for rays in (8, 16, 32):
+            what = f"xl {name} {w}x{h} r{rays}"
+            for debug in (0, 1024, 2048):
+                sc.options(kernel=3, tile_order=2, rays=rays, coarse=8, debug=debug)
+                _kd(sc, want[False], 3, xf, what=f"{what} debug {debug}")
+                if debug == 2048:
+                    assert sc.get_option(_lib.RT_OPT_FAST_USED) == 0, what
+                _kd(sc, want[True], 3, xf, shadow=True, what=f"{what} debug {debug} shadow")
+            sc.options(debug=0)
+            for items in (1, 2, 96):
+                sc.options(items=items)
+                _kd(sc, want[False], 3, xf, what=f"{what} items {items}")
+            sc.options(items=2, pool_cap=89)
+            _kd(sc, want[False], 3, xf, what=what + " pool 89")
+            sc.options(pool_cap=640)
+            for coarse, debug in COARSE + [(8, 4 | 2048)]:
+                sc.options(coarse=coarse, debug=debug or 0)
+                _kd(sc, want[False], 3, xf, what=f"{what} coarse {coarse} debug {debug}")
+                _kd(sc, want[True], 3, xf, shadow=True, what=f"{what} coarse {coarse} debug {debug} shadow")
+        assert sc.cam.device_error() == 0
+    finally:
+        sc.close()
+
+
 # ---------------------------------------------------------------- scale sweep
 
 @pytest.mark.parametrize("e", S.SCALE_EXPONENTS + (S.DENORMAL_EXPONENT,))
@@ -327,6 +394,10 @@ def _tree_case(v, f, name, nodes):
             for kernel in (2, 3):
                 sc.options(kernel=kernel, tile_order=2, rays=16)
                 _kd(sc, sc.oracle(0, xform=xf), kernel, xf, what=f"tree {name} k{kernel} moved")
+            # the moved built tree proves the float walks under a transform; the
+            # trees that raise kCamUnordered or kCamSplitFields keep the double forms
+            proved = S.XLATE_FAST_USED if name in ("built", "shrunk") else 0
+            assert sc.get_option(_lib.RT_OPT_FAST_USED) == proved, (name, xf[[3, 7, 11]])
         assert sc.cam.device_error() == 0
     finally:
         sc.close()

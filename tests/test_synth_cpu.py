@@ -786,3 +786,116 @@ def test_a_wrong_kernel_fails_the_comparison():
     sc = S.SynthScene(*S.light_tie(), S.W, S.H_, cam_kw=S.THRESHOLD_CAM)
     ok, bad = one(*twin(sc), 1, le=True)
     assert (bad[0] == ok[0]).all() and (ok[1][4], bad[1][4]) == (58, 106)
+
+
+# ------------------------------------------- translated walks on exact split values
+# What tests/test_gpu_synth.py's translated grid cases hold, on the two oracles.
+
+def test_xl_offsets_are_split_planes_of_the_built_tree():
+    """What _xl_cases says of grid()'s built tree, at every scale of the table:
+    relative to the eye its x splits (s2) are 0, +-0.15, -0.2 and -0.3, its y
+    splits 0 alone, with an s1 at 0.17 - 0.1, and its z splits lie at 1 (the
+    tiles' plane; s == +1 at every pixel of an unmoved grid); the root box's
+    near face is 0.4 in front of the eye (the z cases)."""
+    for e in (0, 2, 3):
+        sc = S.xl_grid(e)
+        P = S.np_scene(sc)
+        k = F(2.0) ** F(e)
+        inner = [vx for vx in P["vox"] if not vx["leaf"]]
+        s2 = [{float(vx["s2"]) for vx in inner if vx["cf"][axis] == 1} for axis in range(3)]
+        assert s2[0] == {float(F(F(x) * k)) for x in (0, 0.15, -0.15, -0.2, -0.3)}, (e, s2)
+        assert s2[1] == {0.0} and s2[2] == {float(k)}, (e, s2)
+        assert float(F(F(F(0.17) * k) - F(F(0.1) * k))) in {float(vx["s1"]) for vx in inner if vx["cf"][1] == 1}
+        assert P["vox"][0]["bo"][2] == F(F(F(-0.6) * k) - F(F(-1.0) * k))
+    assert F(F(0.17) - F(0.1)) == F(np.float64(F(0.17)) - np.float64(F(0.1)))   # (an exact difference)
+
+
+@pytest.mark.parametrize("name", list(S.XL_CASES))
+def test_xl_case_reaches_its_classes(name):
+    """Each case of XL_CASES at 33x19: the C oracle and the numpy restatement
+    agree on frame, hit buffer and counters; the walk that classifies the
+    visits is the oracle's (xl_classes asserts its visits and descents, and its
+    frame, against the C oracle); the recorded counts are the classifier's; and
+    every class the case is in the table for has at least 8 visits.  The cases
+    with exact zeros are anchored at GRID_FRAMES' other frames too."""
+    e, xf, classes, _ = S.XL_CASES[name]
+    sc = S.xl_grid(e)
+    _anchor(sc, 0, xf, what=f"xl {name}")
+    got = S.xl_classes(sc, xf)
+    print(name, dict(zip(S.XL_CLASSES, got)))
+    assert got == S.XL_COUNTS[name], (name, got)
+    for c in classes:
+        assert got[S.XL_CLASSES.index(c)] >= 8, (name, c, got)
+    assert (xf.reshape(3, 4)[:, 3] != 0).any()           # an offset: the translated walk
+    if name in S.XL_ALL_FRAMES:
+        for w, h in S.GRID_FRAMES[1:]:
+            _anchor(S.xl_grid(e, w, h), 0, xf, what=f"xl {name} {w}x{h}")
+            _anchor(S.xl_grid(e, w, h), 0, xf, shadow=True, what=f"xl {name} {w}x{h} shadow")
+    _anchor(sc, 0, xf, shadow=True, what=f"xl {name} shadow")
+
+
+def test_xl_table_reaches_every_class():
+    """Over the table every class of XL_CLASSES is reached by a case that is
+    listed for it: all four combinations of lt / gt with s == -1 / s == +1
+    among them; each by a case that proves the translated float walk
+    (RT_OPT_FAST_USED & 4, asserted on the GPU), and each by a case with a
+    rotation too, but the guard's far side (guard+-, below+-, tiny-), which
+    the rotation does not change."""
+    assert set(S.XL_COUNTS) == set(S.XL_CASES)
+    listed = {c: [n for n, case in S.XL_CASES.items() if c in case[2]] for c in S.XL_CLASSES}
+    for c, names in listed.items():
+        assert names, c
+        assert any(S.XL_CASES[n][3] for n in names), c
+        assert all(S.XL_COUNTS[n][S.XL_CLASSES.index(c)] >= 8 for n in names), c
+        if c not in ("guard+", "guard-", "below+", "below-", "tiny-"):
+            assert any((S.XL_CASES[n][1].reshape(3, 4)[:, :3] != np.eye(3, dtype=F)).any() for n in names), c
+    assert {"lt_-1", "gt_-1", "lt_+1", "gt_+1"} <= set(listed)
+    # the one offset the suite had before reaches none of the tie or tiny classes
+    old = S.xl_classes(S.xl_grid(0), S.rot_y(0.0, (0.01, -0.005, 0.02)))
+    assert [old[S.XL_CLASSES.index(c)] for c in ("s0x", "s0y", "s0z", "tiny+", "tiny-", "guard+", "guard-", "lt_eq<1",
+                                                     "lt_eq>1")] == [0] * 9
+
+
+class _NumpyKernel:
+    """A numpy restatement of a kernel in the place of a SynthScene's live
+    camera: render() as test_gpu_synth._kd calls it."""
+
+    def __init__(self, sc, form):
+        self.sc, self.form, self.out = sc, form, {}
+
+    def render(self, mode, xform=None, count=False, shadow=False):
+        assert mode == 0 and not shadow
+        if not self.out:
+            self.out[0] = S.xl_render(self.sc, xform, self.form)
+        argb, hit, cnt = self.out[0]
+        return argb, hit, cnt if count else None
+
+
+def test_xl_float_forms_pass_the_comparison():
+    """xfast_slot's forms restated (lt_eps_x / gt_eps_x, the double forms for
+    |s| < 2^-20, s1 in double) give the oracle's frame, hit buffer and counters
+    on every case: the comparison of the GPU tests passes them."""
+    from tests.test_gpu_synth import _kd
+    for name, (e, xf, _, _) in S.XL_CASES.items():
+        sc = S.xl_grid(e)
+        _kd(_NumpyKernel(sc, "float"), sc.oracle(0, xform=xf), 3, xf, what=f"xl {name} float forms")
+
+
+@pytest.mark.parametrize("fault", S.XL_FAULTS)
+def test_xl_a_wrong_kernel_fails_the_comparison(fault):
+    """Five plausible wrong kernels (XL_FAULTS) restated in numpy and fed to
+    the comparison the GPU tests use (test_gpu_synth._kd, as kernel 3): each
+    fails it on the case XL_CATCHES names, on which the faultless float forms
+    pass.  (a) is caught by the case with a rotation of 2^-60 alone: a tiny
+    lane's float compare differs from the double form only where maxt0 * dir
+    or mint1 * dir lies within 1e-16 of s without being equal to it, which
+    takes a ray component below 2^-33; the frames without that rotation have
+    exact zeros there, and 0 == s is decided alike by both."""
+    from tests.test_gpu_synth import _kd
+    name = S.XL_CATCHES[fault]
+    e, xf, _, _ = S.XL_CASES[name]
+    sc = S.xl_grid(e)
+    want = sc.oracle(0, xform=xf)
+    _kd(_NumpyKernel(sc, "float"), want, 3, xf, what=f"xl {name} float forms")
+    with pytest.raises(AssertionError):
+        _kd(_NumpyKernel(sc, fault), want, 3, xf, what=f"xl {name} {fault}")
