@@ -25,6 +25,7 @@ RT_FLAG_SHADOW = 4
 RT_FLAG_FRAME_OUT = 8
 RT_FLAG_WRITE_AOV = 16
 RT_AOV_PLANES = 10
+RT_LIGHTS_MAX = 8
 RT_OPT_KERNEL = 1
 RT_OPT_TILE_ORDER = 2
 RT_OPT_RAYS = 3
@@ -118,6 +119,10 @@ SIGNATURES = {
     "rt_render_display": (C.c_int, [_P, _P, C.c_uint32, C.c_uint32, C.POINTER(RtTile), _P, _P, _P, _P]),
     "rt_render_over": (C.c_int, [_P, _P, C.c_uint32, C.c_uint32, C.POINTER(RtTile), _P, _P, C.c_int64, _P]),
     "rt_shadow_over": (C.c_int, [_P, _P, C.c_uint32, C.POINTER(RtTile), _P, _P, C.c_int64, C.c_int32, _P]),
+    "rt_camera_set_lights": (C.c_int, [_P, _P, C.c_int32]),
+    "rt_camera_get_lights": (C.c_int, [_P, _P, C.POINTER(C.c_int32)]),
+    "rt_light_over": (C.c_int, [_P, _P, C.c_uint32, C.POINTER(RtTile), _P, _P, C.c_int64, _P]),
+    "rt_shade_lights": (C.c_int, [_P, C.c_uint32, C.POINTER(RtTile), _P, _P, _P]),
     "rt_render_clear": (C.c_int, [_P, C.c_uint32, C.POINTER(RtTile), _P, _P, _P]),
     "rt_camera_targets": (C.c_int, [_P, C.POINTER(_P), C.POINTER(_P), C.POINTER(_P), C.POINTER(C.c_int64)]),
     "rt_tile_packed_pixels": (C.c_int64, [C.c_int32, C.c_int32, C.c_int32]),

@@ -62,6 +62,12 @@ struct rt_camera {
     int64_t* d_aov_hit = nullptr;
     unsigned long long* d_counters = nullptr;
     int32_t* d_err = nullptr;
+    // rt_camera_set_lights: the light list (Lx, Ly, Lz, I) x nlights, its host
+    // copy and the device copy rt_light_over / rt_shade_lights read; no other
+    // entry point looks at it (their light is the literal (2, 2, 2))
+    float lights[4 * RT_LIGHTS_MAX] = {2.0f, 2.0f, 2.0f, 1.0f};
+    int32_t nlights = 1;
+    float* d_lights = nullptr;
     rt_scene* obj = nullptr;
     uint64_t prepared_version = 0;
     float4* d_trec = nullptr;        // camera-relative triangle records
@@ -657,6 +663,8 @@ extern "C" int rt_camera_create(int device, int32_t w, int32_t h, float f_w, flo
         (rc = dev_alloc(&c->d_hit, npix, "hipMalloc(hit)")) ||
         (rc = dev_alloc(&c->d_counters, 5, "hipMalloc(counters)")) ||
         (rc = dev_alloc(&c->d_err, 1, "hipMalloc(err)")) ||
+        (rc = dev_alloc(&c->d_lights, 4 * RT_LIGHTS_MAX, "hipMalloc(lights)")) ||
+        (rc = hip_check(hipMemcpy(c->d_lights, c->lights, sizeof c->lights, hipMemcpyHostToDevice), "H2D lights")) ||
         // init_cam_mem_cuda (TD/Camera.cu:97-110): frame zeroed, rmi = -1
         (rc = hip_check(hipMemset(c->d_argb, 0, npix * sizeof(uint32_t)), "memset argb")) ||
         (rc = hip_check(hipMemset(c->d_hit, 0xFF, npix * sizeof(int64_t)), "memset hit")) ||
@@ -1099,6 +1107,157 @@ extern "C" int rt_shadow_over(rt_camera* c, const float* xform, uint32_t flags, 
     return launch_shadow_over(p, (flags & RT_FLAG_COUNT) != 0, stream);
 }
 
+// The light list (rt_light_over, rt_shade_lights).  Not stream-ordered: the
+// device copy is rewritten after the device has drained, so no pass in flight
+// reads a half-written list.
+extern "C" int rt_camera_set_lights(rt_camera* c, const float* lights4, int32_t n) {
+    if (!c) return fail(RT_ERR_INVALID, "rt_camera_set_lights: null camera");
+    if (!lights4 || n < 1 || n > RT_LIGHTS_MAX)
+        return fail(RT_ERR_INVALID, "rt_camera_set_lights: %d lights (1..%d)", n, RT_LIGHTS_MAX);
+    for (int k = 0; k < 4 * n; k++)
+        if (!std::isfinite(lights4[k]))
+            return fail(RT_ERR_INVALID, "rt_camera_set_lights: light %d has a non-finite component", k / 4);
+    DeviceGuard g(c->device);
+    float next[4 * RT_LIGHTS_MAX] = {};
+    memcpy(next, lights4, sizeof(float) * 4 * (size_t)n);
+    int rc;
+    if ((rc = hip_check(hipDeviceSynchronize(), "rt_camera_set_lights: synchronize")) ||
+        (rc = hip_check(hipMemcpy(c->d_lights, next, sizeof next, hipMemcpyHostToDevice), "H2D lights")))
+        return rc;
+    memcpy(c->lights, next, sizeof next);
+    c->nlights = n;
+    return RT_OK;
+}
+
+extern "C" int rt_camera_get_lights(rt_camera* c, float* lights4, int32_t* n) {
+    if (!c) return fail(RT_ERR_INVALID, "rt_camera_get_lights: null camera");
+    if (lights4) memcpy(lights4, c->lights, sizeof(float) * 4 * (size_t)c->nlights);
+    if (n) *n = c->nlights;
+    return RT_OK;
+}
+
+// What rt_light_over and rt_shade_lights share with rt_shadow_over: the
+// targets' defaults, the plane target's checks, and the launch parameters of
+// a pass over every tile of the rank's frame (the camera's caches stay as the
+// renders left them).  tile_h: rows of a block's tile.
+static int light_pass_params(rt_camera* c, const char* who, const float* xform, const rt_tile* tile, bool frame_out,
+                             uint32_t*& d_argb, int64_t*& d_hit, int32_t tile_h, TraceParams& p) {
+    int rc = check_tile(tile);
+    if (rc) return rc;
+    if (d_argb && !d_hit) return fail(RT_ERR_INVALID, "%s: a frame without its hit buffer (the owner is needed)", who);
+    if (!d_argb) {
+        d_argb = c->d_argb;
+        if (!d_hit) d_hit = c->d_hit;
+    }
+    const int32_t nr = tile ? tile->nranks : 1, rk = tile ? tile->rank : 0;
+    // the planes are read, never written: the bound ones (the caller's to
+    // fill, and to size) or the camera's own once something filled them
+    float* aov = c->aov_bound;
+    int64_t stride = c->aov_bound_stride;
+    if (aov) {
+        const int64_t need = nr > 1 && !frame_out ? rt_tile_packed_pixels(c->w, c->h, nr) : (int64_t)c->w * c->h;
+        if (stride < need)
+            return fail(RT_ERR_INVALID, "%s: plane stride %lld is below the %lld pixels this pass reads", who,
+                        (long long)stride, (long long)need);
+    } else {
+        if (!c->d_aov || !c->aov_filled)
+            return fail(RT_ERR_STATE, "%s: the camera's own planes hold no frame (render with RT_FLAG_WRITE_AOV or "
+                                      "rt_render_clear first)", who);
+        aov = c->d_aov;
+        stride = rt_tile_packed_pixels(c->w, c->h, 1);
+    }
+    p.argb = d_argb;
+    p.hit = d_hit;
+    p.counters = c->d_counters;
+    p.err = c->d_err;
+    for (int k = 0; k < 3; k++) {
+        p.n_mod[k] = c->basis.n_mod[k];
+        p.u_mod[k] = c->basis.u_mod[k];
+        p.v_mod[k] = c->basis.v_mod[k];
+    }
+    memcpy(p.xf, xform ? xform : kIdentXf, sizeof p.xf);
+    p.w = c->w;
+    p.h = c->h;
+    p.nranks = nr;
+    p.rank = rk;
+    p.frame_out = frame_out ? 1 : 0;
+    p.tile_w = 8;
+    p.tile_h = tile_h;
+    const int32_t nbands = (c->h + kTileH - 1) / kTileH;
+    p.tiles_x = (c->w + p.tile_w - 1) / p.tile_w;
+    p.block_rows = ((nbands + nr - 1) / nr) * (kTileH / p.tile_h);
+    p.tile_order = c->tile_order == 0 ? 0 : 1;  // as rt_shadow_over
+    p.two_depth = -1;
+    p.debug = c->debug;
+    p.aov = aov;
+    p.aov_stride = stride;
+    p.lights = c->d_lights;
+    p.nlights = c->nlights;
+    return RT_OK;
+}
+
+// The visibility pass of the light list (k_light_kd3): rt_shadow_over's
+// launch with the camera's lights, every hit pixel tested.
+extern "C" int rt_light_over(rt_camera* c, const float* xform, uint32_t flags, const rt_tile* tile, uint32_t* d_argb,
+                             int64_t* d_hit, int64_t hit_base, void* stream) {
+    if (!c) return fail(RT_ERR_INVALID, "rt_light_over: null camera");
+    if (flags & ~(RT_FLAG_COUNT | RT_FLAG_FRAME_OUT))
+        return fail(RT_ERR_INVALID, "rt_light_over: flags 0x%x (RT_FLAG_COUNT and RT_FLAG_FRAME_OUT are accepted)", flags);
+    if (hit_base < 0) return fail(RT_ERR_INVALID, "rt_light_over: hit_base %lld", (long long)hit_base);
+    int rc = check_tile(tile);
+    if (rc) return rc;
+    if (d_argb && !d_hit) return fail(RT_ERR_INVALID, "rt_light_over: a frame without its hit buffer (the owner is needed)");
+    if (c->kernel_version != 3)
+        return fail(RT_ERR_INVALID, "rt_light_over: shadow rays run in the wave-cooperative kernel (3); kernel %d",
+                    c->kernel_version);
+    if (!c->obj) return fail(RT_ERR_STATE, "camera has no object (rt_camera_add_object)");
+    if (!c->obj->d_nodes) return fail(RT_ERR_STATE, "rt_light_over: needs rt_scene_set_kd (Trixel::create_kd) first");
+    if (c->obj->ntri == 0) return fail(RT_ERR_STATE, "rt_light_over: empty scene");
+    TraceParams p{};
+    if ((rc = light_pass_params(c, "rt_light_over", xform, tile, (flags & RT_FLAG_FRAME_OUT) != 0, d_argb, d_hit,
+                                kd3_waves(16) * 2, p)))
+        return rc;
+    DeviceGuard g(c->device);
+    if ((rc = prepare_camera_object(c))) return rc;
+    const rt_scene* s = c->obj;
+    p.inode = c->d_inode;
+    p.trec = c->d_trec;
+    p.split_planes = (c->cam_flags & kCamSplitFields) ? c->d_split : nullptr;
+    p.leaf_off = c->leaf_off;
+    p.rec_bytes = c->leaf_off ? (uint32_t)(c->leaf_off + 64 * (uint64_t)s->ntri) : 0u;
+    p.shade = s->d_shade;
+    p.rays = 16;  // four 16-pixel units per 8 x 8 tile
+    camera_relative_box(s->root, c->pos, p.root_box);
+    p.root_ref = s->root_ref;
+    p.ntri = s->ntri;
+    p.max_depth = kMaxDepth;
+    p.tree_height = s->height;
+    p.tiny_s1 = (c->cam_flags & kCamTinyS1) ? 1 : 0;
+    p.plain_xf = 0;
+    p.fast = p.fast_sh = 0;  // the double forms (k_light_kd3's comment)
+    p.pool_cap = c->pool_cap;
+    p.items = c->items;
+    // a fixed push order as given; timed (-1): the order in use, no timing frames here
+    p.any_order = (c->shadow_order >= 0 ? c->shadow_order : c->any_best) | ((c->debug & 16) ? 4 : 0);
+    p.hit_base = hit_base;
+    return launch_light_over(p, (flags & RT_FLAG_COUNT) != 0, stream);
+}
+
+// The shading pass of the light list (k_shade_lights): no tree, no object.
+extern "C" int rt_shade_lights(rt_camera* c, uint32_t flags, const rt_tile* tile, uint32_t* d_argb, int64_t* d_hit,
+                               void* stream) {
+    if (!c) return fail(RT_ERR_INVALID, "rt_shade_lights: null camera");
+    if (flags & ~RT_FLAG_FRAME_OUT)
+        return fail(RT_ERR_INVALID, "rt_shade_lights: flags 0x%x (RT_FLAG_FRAME_OUT is accepted)", flags);
+    TraceParams p{};
+    int rc = light_pass_params(c, "rt_shade_lights", nullptr, tile, (flags & RT_FLAG_FRAME_OUT) != 0, d_argb, d_hit,
+                               kTileH, p);
+    if (rc) return rc;
+    DeviceGuard g(c->device);
+    p.rays = 8 * kTileH;  // one pixel per lane: an 8 x 8 tile per wave
+    return launch_shade_lights(p, stream);
+}
+
 extern "C" int rt_camera_targets(rt_camera* c, uint32_t** d_argb, int64_t** d_hit, float** d_aov, int64_t* plane_stride) {
     if (!c) return fail(RT_ERR_INVALID, "rt_camera_targets: null camera");
     const int64_t stride = rt_tile_packed_pixels(c->w, c->h, 1);
@@ -1374,6 +1533,7 @@ extern "C" void rt_camera_destroy(rt_camera* c) {
     dev_free(c->d_aov_hit);
     dev_free(c->d_counters);
     dev_free(c->d_err);
+    dev_free(c->d_lights);
     dev_free(c->d_cam_flags);
     dev_free(c->d_split);
     dev_free(c->d_rec);

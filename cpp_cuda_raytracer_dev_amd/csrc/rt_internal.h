@@ -99,6 +99,11 @@ int launch_trace(const TraceParams& p, uint32_t mode, uint32_t flags, int kernel
 // rt_shadow_over's pass (rt_shadow_dispatch.hip): k_shadow_kd3 over the
 // tiles_x * block_rows tiles of p, push order p.any_order.
 int launch_shadow_over(const TraceParams& p, bool count, void* stream);
+// rt_light_over's pass (rt_light_dispatch.hip): k_light_kd3 over the same
+// grid for p.nlights lights; and rt_shade_lights' k_shade_lights, one 8 x 8
+// tile per 64-thread block over the tiles_x * block_rows tiles of p.
+int launch_light_over(const TraceParams& p, bool count, void* stream);
+int launch_shade_lights(const TraceParams& p, void* stream);
 // Camera-relative box of one world node, exactly as init_cam_voxel_mem_cuda.
 void camera_relative_box(const rt_kd_node& nd, const float pos[3], float out[6]);
 // KD build on the GPU (kd_build_gpu.hip).  The median tree's shape depends

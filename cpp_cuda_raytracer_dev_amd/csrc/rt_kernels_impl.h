@@ -103,6 +103,38 @@ __device__ __forceinline__ uint32_t phong(const float pnt[3], const float nrm[3]
     return (to_u8((pr / mx) * 255) << 16) | (to_u8((pg / mx) * 255) << 8) | to_u8((pb / mx) * 255);
 }
 
+// rt_shade_lights: color_cam_cuda's commented-out loop over lights
+// (TD/Camera.cu:29-54, "//FOR EACH LIGHT") closed over a list.  lights: n x
+// (Lx, Ly, Lz, I); occ: bit l set = light l is occluded at this pixel and
+// adds nothing.  Per light the terms are phong()'s with L - pnt for 2 - pnt;
+// the accumulation is c += I * ((rad * diff) + (1 * spec)) in index order,
+// and one normalisation by the largest channel follows, as the reference's
+// point_rad += ... / max_rad is written.  With the list ((2, 2, 2, 1)) and
+// occ = 0 this is phong() bit for bit (0 + x and 1 * x are exact); with every
+// light occluded 0 / 0 goes through to_u8: 0x00000000.
+__device__ __forceinline__ uint32_t phong_lights(const float pnt[3], const float nrm[3], const float rmd[3],
+                                                 const float rad[3], const float* lights, int n, uint32_t occ) {
+    float pr = 0.0f, pg = 0.0f, pb = 0.0f;
+    for (int l = 0; l < n; l++) {
+        if ((occ >> l) & 1u) continue;
+        const float in = lights[4 * l + 3];
+        float sdx = lights[4 * l] - pnt[0], sdy = lights[4 * l + 1] - pnt[1], sdz = lights[4 * l + 2] - pnt[2];
+        const float r = rsqrt21(sdx, sdy, sdz);
+        sdx *= r; sdy *= r; sdz *= r;
+        const float dot_r_n = dot3(sdx, sdy, sdz, nrm[0], nrm[0], nrm[2]);
+        const float rx = (sdx - (2 * dot_r_n * nrm[0])) * rmd[0];
+        const float ry = (sdy - (2 * dot_r_n * nrm[1])) * rmd[1];
+        const float rz = (sdz - (2 * dot_r_n * nrm[2])) * rmd[2];
+        const float diff = (float)(.6 * (double)fabsf(dot_r_n));
+        const float spec = (float)((double)pow5(fabsf((rx + ry + rz))) * .3);
+        pr = pr + (in * ((rad[0] * diff) + (1 * spec)));
+        pg = pg + (in * ((rad[1] * diff) + (1 * spec)));
+        pb = pb + (in * ((rad[2] * diff) + (1 * spec)));
+    }
+    const float mx = fmaxf(fmaxf(pr, pg), pb);
+    return (to_u8((pr / mx) * 255) << 16) | (to_u8((pg / mx) * 255) << 8) | to_u8((pb / mx) * 255);
+}
+
 // A pixel's frame write.  With P.display (rt_render_display) it also writes
 // the reference's displayed frame: the clean buffer argb still holds the
 // previous frame, which a miss keeps on screen (ghosting under motion: the
@@ -2574,6 +2606,168 @@ __global__ RT_KD3_BOUNDS(64 * kd3_waves(16)) void k_shadow_kd3(TraceParams P) {
     }
 }
 
+// rt_light_over: k_shadow_kd3's pass for a list of lights (P.lights, P.nlights
+// x (Lx, Ly, Lz, I)).  Every hit pixel of the composite is tested (there is no
+// skip_own); for light l the segment is k_shadow_kd3's with L_l for the
+// literal 2 -- s = ((d*r) - od) - L_l per component in that order, Lmax =
+// sqrtf(s.s) * 0.9990234375f, the direction by rsqrt21, the ray's offset
+// (-Lx, -Ly, -Lz) -- with the same exclusion of the pixel's own triangle where
+// the pixel is this object's.  Where the walk finds an occluder the pass sets
+// bit 24 + l of the pixel's frame word (every frame writer stores a zero top
+// byte; rt_shade_lights reads the byte and overwrites the word), and that one
+// plain store per pixel, issued only where a new bit was found, is the pass's
+// only store: one lane owns a pixel, so no atomic is needed, and since the
+// pass only ORs it is idempotent and the passes of several objects commute.
+// A timed pass does not walk a light whose bit is set on entry (exact: the
+// bit could only be set again); a counted one walks every light of every
+// tested pixel, so its counters do not depend on the order of the passes.
+// The loop over the lights is wave-uniform: a light none of the unit's lanes
+// needs is skipped, otherwise the ray fields, keys and pool in LDS are set up
+// again and the walk runs as k_shadow_kd3's does.
+// The walk takes the double forms (kWalkRef), which read the ray's offset and
+// its per-axis ds from LDS fields 6-8 (store_ray, ray_of) and the slab
+// offsets od / r from fields 3-4 (finish_ray): no visit assumes od = (-2, -2,
+// -2).  The light's proof for the float forms (fast_proof_shadow, xfast_slot)
+// does, and is not used here.
+// Any bit pattern in plane 0 or in the frame's top byte terminates: per light
+// it is k_shadow_kd3's argument (a traversal of a finite tree, rsqrt21's fixed
+// 21 steps, a NaN d makes Lmax NaN and the pool empty), and the light loop
+// runs P.nlights <= RT_LIGHTS_MAX times whatever the data.
+template <bool kCount, int kOrder>
+__global__ RT_KD3_BOUNDS(64 * kd3_waves(16)) void k_light_kd3(TraceParams P) {
+    constexpr int kRays = 16, kCap = pool_cap_for<kRays>(), kRayVec = 5;
+    using RL = RayLayout<kRays>;
+    __shared__ WaveLds<kRays, kCap, kRayVec> s_lds[kd3_waves(kRays)];
+    const int wv = wave_id(), lane = (int)threadIdx.x & 63;
+    const int32_t b = (int32_t)blockIdx.x, ntiles = P.tiles_x * P.block_rows;
+    if (b >= ntiles) return;
+    const int32_t ti = tile_index(P, b);
+    if ((uint32_t)ti >= (uint32_t)ntiles) return;  // (orders 0 and 1 are bijections; never index past the grid)
+    WaveLds<kRays, kCap, kRayVec>& S_ = s_lds[wv];
+    const Unit U = unit_of_tile(P, ti, wv);
+    Pixel px;
+    const bool live = unit_pixel(P, U, kRays / 8, lane, px);
+    const int64_t h = live ? P.hit[px.out] : (int64_t)-1;
+    const bool own = h >= P.hit_base && h < P.hit_base + (int64_t)P.ntri;
+    const bool test = live && h >= 0;
+    if (__ballot(test) == 0ull) return;
+    const float d = test ? P.aov[px.out] : 0.0f;
+    // What a lane keeps from one light to the next waits in its ray's slots of
+    // the wave's LDS, not in registers held across the walks (which cost the
+    // kernel a wave per SIMD): the depth in rn, the frame word -- which also
+    // collects the bits this pass finds; bit 24 + l is looked at in iteration
+    // l alone, before that iteration sets it -- in tri, which an any-hit walk
+    // leaves alone, and the excluded triangle in the ray's field 9
+    // (store_ray).  The pixel and its ray are recomputed per light.
+    if (lane < kRays) {
+        S_.rn[lane] = d;
+        S_.tri[lane] = test ? P.argb[px.out] : 0u;
+        S_.ray[lane + 9 * RL::kStride].y = __uint_as_float(own ? (uint32_t)(h - P.hit_base) : kMiss);
+    }
+    bool found = false;
+    const int nl = min(max(P.nlights, 0), RT_LIGHTS_MAX);
+    Counts C;
+    for (int l = 0; l < nl; l++) {
+        // the lane index as a value the compiler cannot see through: what it
+        // would otherwise compute once for all lights (LDS addresses, the
+        // pixel) and hold in registers across the walks is made per light
+        int ln = (int)threadIdx.x & 63;
+        asm volatile("" : "+v"(ln));
+        // a timed pass: the lights this pixel's mask does not hold yet
+        const uint32_t word = ln < kRays ? S_.tri[ln] : 0u;
+        const bool need = test && (kCount || ((word >> (24 + l)) & 1u) == 0u);
+        if (__ballot(need) == 0ull) continue;
+        const float lx = P.lights[4 * l], ly = P.lights[4 * l + 1], lz = P.lights[4 * l + 2];
+        // the shadow segment of the stored hit: from light l to H = d*r - od
+        Ray Sh;
+        Sh.odx = -lx; Sh.ody = -ly; Sh.odz = -lz;
+        Sh.rx = 1.0f; Sh.ry = 1.0f; Sh.rz = 1.0f;
+        float lmax = 0.0f;
+        {
+            Pixel q;
+            unit_pixel(P, U, kRays / 8, ln, q);
+            float cam[3];
+            Ray R;
+            camera_ray(P, q, need, cam, R);
+            if (need) {
+                const float dd = S_.rn[ln];
+                float sx = ((dd * R.rx) - R.odx) - lx;
+                float sy = ((dd * R.ry) - R.ody) - ly;
+                float sz = ((dd * R.rz) - R.odz) - lz;
+                lmax = sqrtf((sx * sx) + (sy * sy) + (sz * sz)) * 0.9990234375f;  // correctly rounded sqrt
+                const float r = rsqrt21(sx, sy, sz);
+                Sh.rx = sx * r; Sh.ry = sy * r; Sh.rz = sz * r;
+            }
+        }
+        finish_ray(Sh);
+        if (ln < kRays) {
+            const uint32_t self = __float_as_uint(S_.ray[ln + 9 * RL::kStride].y);
+            store_ray(&S_.ray[ln], RL::kStride, Sh, true, lmax, self);
+            S_.key[ln] = ~0ull;
+        }
+        __builtin_amdgcn_wave_barrier();
+        uint32_t iters = 0, popped = 0;
+        const int n = seed_root<kCount, true>(P, S_.items, Sh, need, ln, C.n_int, C.n_desc, lmax);
+        pool_walk<kCap, RL::kStride, true, kCount, true, kOrder>(P, S_.items, S_.ray, S_.key, S_.tri, n, ln, iters,
+                                                                popped, C.n_int, C.n_leaf, C.n_acc, C.n_desc);
+        if (need && S_.key[ln] == 0ull) {
+            const uint32_t was = S_.tri[ln];
+            if (((was >> (24 + l)) & 1u) == 0u) {
+                S_.tri[ln] = was | (1u << (24 + l));
+                found = true;
+            }
+        }
+        __builtin_amdgcn_wave_barrier();  // the keys are read before the next light's set-up stores them
+    }
+    if (found) {  // one plain store per pixel, where a new bit was found
+        Pixel out;
+        int le = (int)threadIdx.x & 63;
+        asm volatile("" : "+v"(le));
+        unit_pixel(P, U, kRays / 8, le, out);
+        P.argb[out.out] = S_.tri[le];
+    }
+    if (kCount) {  // the lights' counted shadow walks, summed; [3] (hit pixels) is the render's
+        wave_count_add(&P.counters[0], C.n_int);
+        wave_count_add(&P.counters[1], C.n_leaf);
+        wave_count_add(&P.counters[2], C.n_acc);
+        wave_count_add(&P.counters[4], C.n_desc);
+    }
+}
+
+// rt_shade_lights: the shading pass over a composite whose frame words carry
+// the lights' visibility mask in their top byte (k_light_kd3).  One pixel per
+// lane, an 8 x 8 tile per wave in the band-slot addressing of every other
+// writer (unit_pixel), so a row of 8 pixels is a 32-byte run of the frame and
+// of each plane.  A hit pixel's word becomes phong_lights() of planes 1-9 and
+// its primary ray, with a zero top byte; a miss gets no store, and nothing
+// else is stored.  No tree is read: the pixel's owner may be any object,
+// rendered by any kernel.
+// kRows: the rows of a wave's tile (one instance, in rt_light_dispatch.hip).
+template <int kRows>
+__global__ __launch_bounds__(8 * kRows) void k_shade_lights(TraceParams P) {
+    const int lane = (int)threadIdx.x & 63;
+    const int32_t b = (int32_t)blockIdx.x, ntiles = P.tiles_x * P.block_rows;
+    if (b >= ntiles) return;
+    const int32_t ti = tile_index(P, b);
+    if ((uint32_t)ti >= (uint32_t)ntiles) return;
+    const Unit U = unit_of_tile(P, ti, 0);
+    Pixel px;
+    if (!unit_pixel(P, U, kRows, lane, px)) return;
+    // the hit index, the frame word and the nine planes, issued together
+    const float* a = P.aov + px.out;
+    const int64_t s = P.aov_stride;
+    const int64_t h = P.hit[px.out];
+    const uint32_t word = P.argb[px.out];
+    const float pnt[3] = {a[s], a[2 * s], a[3 * s]};
+    const float nrm[3] = {a[4 * s], a[5 * s], a[6 * s]};
+    const float rad[3] = {a[7 * s], a[8 * s], a[9 * s]};
+    if (h < 0) return;
+    float rmd[3];
+    primary_ray(P, px.x, px.y, rmd);
+    const int nl = min(max(P.nlights, 0), RT_LIGHTS_MAX);
+    P.argb[px.out] = phong_lights(pnt, nrm, rmd, rad, P.lights, nl, word >> 24);
+}
+
 // The coarse groups (every 8x8 group of this rank outside the fine tiles),
 // P.coarse_per_wave (<= kCoarseMax) per wave.  A separate kernel: looping trace_unit inside
 // the fine kernel costs it a third of its occupancy (80 -> 113 VGPRs).
@@ -3196,6 +3390,27 @@ TraceFn shadow_kernel(int any_order) {
         case 1: return k_shadow_kd3<false, 1>;
         case 2: return k_shadow_kd3<false, 2>;
         default: return k_shadow_kd3<false, 3>;
+        }
+    }
+}
+
+// k_light_kd3's instances: the same nine, selected as shadow_kernel's.
+template <bool C>
+TraceFn light_kernel(int any_order) {
+    if constexpr (C) {
+        switch (any_order) {
+        case 4: return k_light_kd3<true, 4>;
+        case 5: return k_light_kd3<true, 5>;
+        case 6: return k_light_kd3<true, 6>;
+        case 7: return k_light_kd3<true, 7>;
+        default: return k_light_kd3<true, 0>;
+        }
+    } else {
+        switch (any_order & 3) {
+        case 0: return k_light_kd3<false, 0>;
+        case 1: return k_light_kd3<false, 1>;
+        case 2: return k_light_kd3<false, 2>;
+        default: return k_light_kd3<false, 3>;
         }
     }
 }

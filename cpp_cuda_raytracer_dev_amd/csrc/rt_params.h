@@ -124,6 +124,11 @@ struct TraceParams {
     // rt_shadow_over (k_shadow_kd3 alone reads it; last for the same reason):
     // the object's own pixels, hit_base <= hit < hit_base + ntri, are not tested
     int32_t shadow_skip_own;
+    // rt_light_over / rt_shade_lights (k_light_kd3 and k_shade_lights alone
+    // read them; last for the same reason): the camera's light list on the
+    // device, nlights x (Lx, Ly, Lz, I), 1 <= nlights <= RT_LIGHTS_MAX
+    const float* lights;
+    int32_t nlights;
 };
 
 // Blocks of k_trace_kd3's grid (fine tiles, split extras, far fill).

@@ -376,6 +376,8 @@ class Camera:
         layer.add_object(new_object)
         for key, value in getattr(self, "_options", {}).items():
             layer.set_option(key, value)
+        if getattr(self, "_lights", None) is not None:
+            layer.set_lights(self._lights)
         _, _, planes, stride = self.targets()
         layer.set_aov(planes, stride)
         layer._targets = self.targets()[:2]
@@ -482,6 +484,71 @@ class Camera:
         for layer in self._layers.values():
             obj = layer.object_list[-1]
             layer.shadow_over(None, None, obj.quat.xform(), flags, hit_base=obj.hit_base, skip_own=skip_own)
+        return 0
+
+    def set_lights(self, lights) -> None:
+        """rt_camera_set_lights: the camera's light list, 1..RT_LIGHTS_MAX rows
+        (Lx, Ly, Lz, I), read by ``light_over`` / ``shade_lights`` alone; the
+        layers' cameras (``add_layer``) get the same list."""
+        a = np.ascontiguousarray(lights, np.float32)
+        if a.ndim != 2 or a.shape[1] != 4:
+            raise _lib.RtError("Camera.set_lights", -1, "lights: rows of (x, y, z, intensity)")
+        _lib.call("rt_camera_set_lights", self._h, _lib.ptr(a), int(a.shape[0]))
+        self._lights = a.copy()
+        for layer in self._layers.values():
+            layer.set_lights(a)
+
+    @property
+    def lights(self) -> np.ndarray:
+        """rt_camera_get_lights: the light list as an [n, 4] float32 array."""
+        buf = np.zeros((_lib.RT_LIGHTS_MAX, 4), np.float32)
+        n = C.c_int32()
+        _lib.call("rt_camera_get_lights", self._h, _lib.ptr(buf), C.byref(n))
+        return buf[:n.value].copy()
+
+    def light_over(self, argb=None, hit=None, xform=None, flags=0, tile=None, hit_base=0, stream=None) -> int:
+        """rt_light_over: the visibility pass of this camera's object for its
+        light list over the composite in the targets (as ``shadow_over``'s):
+        bit 24 + l of a hit pixel's frame word is set where the object
+        occludes light l, and nothing else is written."""
+        own = getattr(self, "_targets", (None, None))  # a layer camera: its base's buffers
+        if argb is None:
+            argb, hit = own[0], own[1] if hit is None else hit
+        xf = np.ascontiguousarray(xform if xform is not None else Quaternion().xform(), np.float32)
+        t = None if tile is None else C.byref(_lib.RtTile(tile[0], tile[1]))
+        s = C.c_void_p(stream) if isinstance(stream, int) else C.c_void_p(None)
+        a = argb if isinstance(argb, C.c_void_p) else _lib.ptr(argb)
+        h = hit if isinstance(hit, C.c_void_p) else _lib.ptr(hit)
+        _lib.call("rt_light_over", self._h, _lib.ptr(xf), flags, t, a, h, int(hit_base), s)
+        return 0
+
+    def shade_lights(self, argb=None, hit=None, flags=0, tile=None, stream=None) -> int:
+        """rt_shade_lights: every hit pixel of the targets becomes the sum of
+        its unoccluded lights' shading (the frame's top byte is the mask the
+        ``light_over`` passes left), normalised once; a miss is not written."""
+        own = getattr(self, "_targets", (None, None))
+        if argb is None:
+            argb, hit = own[0], own[1] if hit is None else hit
+        t = None if tile is None else C.byref(_lib.RtTile(tile[0], tile[1]))
+        s = C.c_void_p(stream) if isinstance(stream, int) else C.c_void_p(None)
+        a = argb if isinstance(argb, C.c_void_p) else _lib.ptr(argb)
+        h = hit if isinstance(hit, C.c_void_p) else _lib.ptr(hit)
+        _lib.call("rt_shade_lights", self._h, flags, t, a, h, s)
+        return 0
+
+    def light_layers(self, flags=0) -> int:
+        """The frame's objects lit by the camera's light list: after the
+        renders (``obj1.render; obj2.render``), one ``light_over`` for the base
+        object and one for each layer with that object's current transform and
+        hit base, then one ``shade_lights``."""
+        if not self.object_list:
+            raise _lib.RtError("Camera.light_layers", -5, "add the base object (add_object) first")
+        base = self.object_list[-1]
+        self.light_over(None, None, base.quat.xform(), flags, hit_base=base.hit_base)
+        for layer in self._layers.values():
+            obj = layer.object_list[-1]
+            layer.light_over(None, None, obj.quat.xform(), flags, hit_base=obj.hit_base)
+        self.shade_lights(None, None, flags & RT_FLAG_FRAME_OUT)
         return 0
 
     def clear_layers(self, argb=None, hit=None, flags=0, tile=None, stream=None) -> int:

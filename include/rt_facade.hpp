@@ -255,10 +255,14 @@ public:
         layers_.push_back(l);  // owned from here on
         float* planes = nullptr;
         int64_t stride = 0;
+        float lights[4 * RT_LIGHTS_MAX];
+        int32_t nlights = 0;
         if ((rc = new_object->attach_motion(pos_, n_, u_, cam_speed)) ||
             (rc = rt_camera_add_object(l.cam, new_object->trixel_list->handle())) ||
             (rc = rt_camera_targets(cam_, nullptr, nullptr, &planes, &stride)) ||
-            (rc = rt_camera_set_aov(l.cam, planes, stride)))
+            (rc = rt_camera_set_aov(l.cam, planes, stride)) ||
+            (rc = rt_camera_get_lights(cam_, lights, &nlights)) ||  // the layer starts with the frame's light list
+            (rc = rt_camera_set_lights(l.cam, lights, nlights)))
             return rc;
         s64 base = objects_.back()->trixel_list->num_trixels;
         for (size_t k = 0; k + 1 < layers_.size(); k++) base += layers_[k].obj->trixel_list->num_trixels;
@@ -295,6 +299,32 @@ public:
             rc = rt_shadow_over(layers_[k].cam, layers_[k].obj->quat->rot_m, 0u, nullptr, argb, (int64_t*)hit,
                                 layers_[k].obj->hit_base, skip_own ? 1 : 0, nullptr);
         return rc;
+    }
+    // The frame's light list (rt_camera_set_lights): n x (Lx, Ly, Lz, I), given
+    // to every layer's camera here and to a later layer's in add_layer (the
+    // call synchronises the device, so it is kept out of the frame loop).
+    // Only light_layers() reads the list.
+    int set_lights(const float* lights4, int n) {
+        int rc = rt_camera_set_lights(cam_, lights4, n);
+        for (size_t k = 0; !rc && k < layers_.size(); k++) rc = rt_camera_set_lights(layers_[k].cam, lights4, n);
+        return rc;
+    }
+    // Lights the frame's objects by that list: after the renders, one
+    // visibility pass (rt_light_over) for the base object and one for each
+    // layer, each with that object's current transform and hit base, then the
+    // shading pass (rt_shade_lights).  obj1->render; obj2->render;
+    // light_layers(); color_pixels gives the frame lit by every light.
+    int light_layers() {
+        if (objects_.empty()) return RT_ERR_STATE;
+        u32* argb = nullptr;
+        s64* hit = nullptr;
+        int rc = rt_camera_targets(cam_, &argb, (int64_t**)&hit, nullptr, nullptr);
+        const Object* base = objects_.back();
+        if (!rc) rc = rt_light_over(cam_, base->quat->rot_m, 0u, nullptr, argb, (int64_t*)hit, base->hit_base, nullptr);
+        for (size_t k = 0; !rc && k < layers_.size(); k++)
+            rc = rt_light_over(layers_[k].cam, layers_[k].obj->quat->rot_m, 0u, nullptr, argb, (int64_t*)hit,
+                               layers_[k].obj->hit_base, nullptr);
+        return rc ? rc : rt_shade_lights(cam_, 0u, nullptr, argb, (int64_t*)hit, nullptr);
     }
     bool is_layer(const Object* o) const {
         for (auto& l : layers_)

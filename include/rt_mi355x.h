@@ -78,6 +78,8 @@ typedef enum rt_status {
  * transform takes it; rt_run_frames rejects it. */
 #define RT_FLAG_WRITE_AOV 16u
 #define RT_AOV_PLANES 10
+/* Most lights of a camera's list (rt_camera_set_lights). */
+#define RT_LIGHTS_MAX 8
 
 /* Per-triangle AABB = kd_leaf (TD/Trixel.h:31-37); `tri` = tri_list_index. */
 typedef struct rt_leaf_aabb {
@@ -311,6 +313,79 @@ int rt_render_over(rt_camera* c, const float* xform, uint32_t mode, uint32_t fla
  * nothing. */
 int rt_shadow_over(rt_camera* c, const float* xform, uint32_t flags, const rt_tile* tile,
                    uint32_t* d_argb, int64_t* d_hit, int64_t hit_base, int32_t skip_own, void* stream);
+
+/* A light list: deferred shading and shadows of a composite for up to
+ * RT_LIGHTS_MAX lights.  Our definition where the reference stops: its
+ * color_cam_cuda carries the loop over lights commented out, with one light
+ * "at 2,2,2 for now" and the intensity a TODO (TD/Camera.cu:29-54); its
+ * accumulation and single normalisation by the largest channel are what is
+ * closed over a list here.
+ *
+ * A light is four floats (Lx, Ly, Lz, I); a camera holds n of them, 1 <= n <=
+ * RT_LIGHTS_MAX, by default the one light (2, 2, 2, 1).  The position stands
+ * exactly where the literal 2 stands in every other entry point: relative to
+ * the eye at the identity, and under an object transform in that object's
+ * space, so the light moves with the object (as rt_shadow_over's does).
+ * rt_camera_set_lights: n outside 1..RT_LIGHTS_MAX, a null list or any
+ * non-finite float returns RT_ERR_INVALID and leaves the list unchanged.  It
+ * synchronises the device (the list has a small device copy) and is not
+ * stream-ordered.  rt_camera_get_lights copies the list out (either pointer
+ * may be NULL).  rt_render*, RT_FLAG_SHADOW, rt_shadow_over and
+ * rt_run_frames never read the list: their light is the literal.
+ *
+ * Visibility.  rt_light_over is object B's pass (camera c, transform xform),
+ * shaped like rt_shadow_over without skip_own: every addressed pixel p with
+ * hit[p] >= 0 is tested.  B occludes light l at p iff rt_shadow_over's test
+ * with L_l in place of (2,2,2) finds an occluder: with d the float in plane 0
+ * and (r, od) B's object-space ray of p, the segment s = ((d*r) - od) - L_l
+ * component by component in that order, Lmax = sqrtf(s.s) * 0.9990234375f, the
+ * direction s * rsqrt21(s), the ray's offset (-Lx, -Ly, -Lz), the segment
+ * rule and the leaf rule w < Lmax, the one triangle hit[p] - hit_base
+ * excluded when p is B's own pixel and none otherwise.  The walk takes the
+ * double forms.
+ *
+ * Where the visibility lives: a frame word is 0x00RRGGBB and every writer
+ * stores a zero top byte; rt_light_over ORs bit 24 + l into the frame word of
+ * a pixel where B occludes light l.  That store -- one per pixel, only where
+ * a new bit was found -- is the pass's only store.  So there is no extra
+ * buffer and no clear call, the mask follows the frame's own indexing, the
+ * passes are idempotent and commute, and between the visibility passes and
+ * the shading pass the frame is not displayable.  A timed pass does not walk
+ * a light whose bit is set on entry (exact, since the pass only ORs); under
+ * RT_FLAG_COUNT it walks every light of every tested pixel, so the counters
+ * do not depend on the order of the passes: [0], [1], [2], [4] get the sum of
+ * the per-light shadow walks (debug bit 16 stops them at occluders), [3] is
+ * not touched.  Flags: RT_FLAG_COUNT and RT_FLAG_FRAME_OUT.  KD tree and
+ * kernel 3 only; the error contract is rt_shadow_over's (RT_ERR_INVALID under
+ * RT_OPT_KERNEL 2, for d_argb without d_hit, for hit_base < 0, for a short
+ * bound stride; RT_ERR_STATE without a tree or with own planes never filled;
+ * nothing is launched on an error), and RT_OPT_SHADOW_ORDER (-1: the order in
+ * use, no timing frames), RT_OPT_ITEMS, RT_OPT_POOL_CAP and the tile orders
+ * 0 / 1 apply as there.  Plane 0 and the top byte are the caller's data: any
+ * bit pattern terminates with device error 0, and a NaN d occludes nothing.
+ *
+ * Shading.  rt_shade_lights shades every addressed pixel with hit[p] >= 0
+ * from the frame's top byte occ, planes 1-9 of c's plane target (bound or
+ * own) and c's lights: from c = (0, 0, 0), for l = 0 .. n-1 in index order,
+ * skipping l in occ, with sd, dot_r_n (norm.x twice), rx, ry, rz, diff and
+ * spec exactly as the single light's shading computes them from L_l - pnt,
+ * c_k = c_k + (I_l * ((rad_k * diff) + (1 * spec))); then mx = max(c_r, c_g,
+ * c_b) and each channel (u8)((c_k / mx) * 255), no contraction anywhere.  It
+ * stores the colour with a zero top byte at hit pixels and nothing else (a
+ * miss gets no store), so it consumes the mask and is not idempotent.  It
+ * needs no tree and no object: the owners may come from kernel 2 or the flat
+ * list.  Flag: RT_FLAG_FRAME_OUT only.  Same target, state and stride errors.
+ * Consequences: with every light occluded the pixel is 0x00000000 (0 / 0
+ * through the u8 conversion), the shadow colour of every other entry point;
+ * with the default list, overs + rt_light_over per object + rt_shade_lights
+ * is bit for bit the frame overs + rt_shadow_over per object leave (0 + x and
+ * 1 * x are exact). */
+int rt_camera_set_lights(rt_camera* c, const float* lights4, int32_t n);
+int rt_camera_get_lights(rt_camera* c, float* lights4, int32_t* n);
+int rt_light_over(rt_camera* c, const float* xform, uint32_t flags, const rt_tile* tile,
+                  uint32_t* d_argb, int64_t* d_hit, int64_t hit_base, void* stream);
+int rt_shade_lights(rt_camera* c, uint32_t flags, const rt_tile* tile, uint32_t* d_argb, int64_t* d_hit,
+                    void* stream);
 
 /* The miss state into the same targets, for the pixels a render with that
  * tile and RT_FLAG_FRAME_OUT setting (the only flag accepted) addresses: argb

@@ -1,7 +1,7 @@
 // rt_headless.cpp -- the headless frame loop that replaces WinMain
 // (TD/WinMain.cpp:44-249), written against the reference-shaped C++ facade.
 //
-//   rt_headless <mesh.ply> <mode 0|1|2> [w h frames out.ppm flat keys] [--aov planes.f32] [--over KEYS [--cross-shadow]]
+//   rt_headless <mesh.ply> <mode 0|1|2> [w h frames out.ppm flat keys] [--aov planes.f32] [--over KEYS [--cross-shadow | --lights "x,y,z,i;..."]]
 //
 // keys: held keys per frame, cycled, one input tick per frame (WinMain ticks
 // at TICK_RATE, :173): letters of R W S Q E T, '+' joins keys held together,
@@ -53,8 +53,11 @@ int main(int argc, char** argv) {
     // once, and rendered over the first object every frame
     // --cross-shadow (anywhere on the line, with --over): after the two
     // renders of a frame the objects shadow one another (Camera::shadow_layers)
+    // --lights "x,y,z,i;x,y,z,i;..." (anywhere on the line, with --over): the
+    // frame is lit by that list instead (Camera::set_lights, light_layers)
     const char* aov_out = nullptr;
     const char* over_keys = nullptr;
+    const char* lights_arg = nullptr;
     bool cross_shadow = false;
     for (int k = 1; k < argc;) {
         if (std::strcmp(argv[k], "--cross-shadow")) { k++; continue; }
@@ -64,14 +67,28 @@ int main(int argc, char** argv) {
     }
     for (int k = 1; k + 1 < argc;) {
         const bool aov = !std::strcmp(argv[k], "--aov"), over = !std::strcmp(argv[k], "--over");
-        if (!aov && !over) { k++; continue; }
-        (aov ? aov_out : over_keys) = argv[k + 1];
+        const bool lights = !std::strcmp(argv[k], "--lights");
+        if (!aov && !over && !lights) { k++; continue; }
+        (aov ? aov_out : over ? over_keys : lights_arg) = argv[k + 1];
         for (int j = k; j + 2 < argc; j++) argv[j] = argv[j + 2];
         argc -= 2;
     }
-    if (argc < 3 || (cross_shadow && !over_keys)) {
+    std::vector<float> lights;  // x, y, z, i per light
+    if (lights_arg) {
+        for (const char* q = lights_arg; *q;) {
+            char* end = nullptr;
+            lights.push_back(std::strtof(q, &end));
+            if (end == q) { lights.clear(); break; }
+            q = (*end == ',' || *end == ';') ? end + 1 : end;
+        }
+        if (lights.empty() || lights.size() % 4) {
+            std::fprintf(stderr, "--lights: four numbers x,y,z,i per light, lights joined by ';'\n");
+            return 2;
+        }
+    }
+    if (argc < 3 || ((cross_shadow || lights_arg) && !over_keys) || (cross_shadow && lights_arg)) {
         std::fprintf(stderr, "usage: %s mesh.ply mode [w h frames out.ppm flat keys] [--aov planes.f32] "
-                             "[--over KEYS [--cross-shadow]]\n",
+                             "[--over KEYS [--cross-shadow | --lights \"x,y,z,i;...\"]]\n",
                      argv[0]);
         return 2;
     }
@@ -119,6 +136,10 @@ int main(int argc, char** argv) {
         std::fprintf(stderr, "add_object: %s\n", rt_last_error_string());
         return 1;
     }
+    if (lights_arg && main_cam->set_lights(lights.data(), (int)(lights.size() / 4))) {
+        std::fprintf(stderr, "set_lights: %s\n", rt_last_error_string());
+        return 1;
+    }
     if (over_keys)
         for (uint32_t m : parse_keys(over_keys))
             if (obj2->key_tick(m)) { std::fprintf(stderr, "transform: %s\n", rt_last_error_string()); return 1; }
@@ -138,6 +159,10 @@ int main(int argc, char** argv) {
         }
         if (cross_shadow && main_cam->shadow_layers()) {
             std::fprintf(stderr, "shadow_layers: %s\n", rt_last_error_string());
+            return 1;
+        }
+        if (lights_arg && main_cam->light_layers()) {
+            std::fprintf(stderr, "light_layers: %s\n", rt_last_error_string());
             return 1;
         }
         if (main_cam->color_pixels(PHONG_COLOR_TAG)) {
